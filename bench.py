@@ -8,12 +8,14 @@ One "step" = one depth map: the full ``MVSNet.forward`` (FeatureNet + 3 stages x
 synthetic inputs of BASELINE config 2 (DTU eval 1600x1184, 5 views, 64/32/8 hypotheses), inputs resident in
 HBM before the timed region.  N > 1 (default ``--mode auto``): the timed region runs the N ranks as independent replicas --
 every rank processes its own reference views (the depth maps of a scan are independent units): no data-path
-collective, weak scaling, this is `value` -- and THE SAME LINE then carries `latency_mode`: north_star's partition, the source
+collective, weak scaling, this is `value` -- and with --full THE SAME LINE then carries `latency_mode`: north_star's partition, the source
 views of ONE depth map sharded over a view group with RCCL on the data path (reduce_scatter along H + halo send / recv +
 all-gather, H-slab regularisation; view group = the largest divisor of N that is <= V - 1, so 5 views on 8 GPUs run as 2 groups
 x 4), with the bytes every collective moved per rank and `depth_rel_vs_unsharded` measured in the run.
 
-Rank 0 prints ONE JSON line.  Besides the driver's keys it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps depth maps and prints it (--dump-outputs DIR: the last
+step's outputs as .npy files, written after the timed region).  --full also runs the context legs outside the timed region;
+the line then carries besides the driver's keys
   roofline      dominant kernel family (by time), HIP-event timed inside the timed region
   roofline_all  the same for every kernel family
   ms_per_stage  HIP-event spans of features / stage1 / stage2 / stage3
@@ -51,9 +53,16 @@ def parse():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c2")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the context legs outside the timed region: the replicas pass and the latency leg of the multi-GPU "
+                         "modes, the full-outputs pass, the per-kernel roofline pass with its single-stream / PMC / K1 child runs, "
+                         "the CPU baseline with `parity`, and the ATen-on-GPU baseline.  Without it the command sets up, warms up, "
+                         "times --steps depth maps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--mode", default="auto", choices=["auto", "replicas", "view-shard", "view-shard-rows"],
                     help="N > 1: auto (default, what the driver's scaling runs time) = `value` from N replicas (one depth map per rank, "
-                         "no data-path collective, weak scaling) AND, in the same line, `latency_mode` from the hybrid view shard "
+                         "no data-path collective, weak scaling) AND, with --full, in the same line `latency_mode` from the hybrid view shard "
                          "(view-shard-rows with --view-group = the largest divisor of N that is <= V - 1: N = 2 -> 2, 4 -> 4, 8 -> 2 "
                          "groups x 4 at 5 views) with the bytes per collective per rank and depth_rel_vs_unsharded; replicas = only "
                          "the replicas; view-shard-rows (v2) = ONE depth map over a view group: source views sharded, reduce_scatter "
@@ -417,6 +426,34 @@ def pmc_traffic(live_text=None):
     return out
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: all .npy files together stay under 64 MB
+
+
+def dump_outputs(out, path):
+    """Write the forward's output dict as ``path/<name>.npy``: the stage dicts flattened (``stage1.depth``, ...), then any
+    top-level tensor that is not one of them (the top-level entries of the last stage are the same tensors, written once).
+    float64 stays float64, every other dtype is written as float32.  Each array gets an equal share of DUMP_BYTES; one larger
+    than its share is written as a fixed sample of its flattened values, at the sorted flat indices
+    ``np.random.default_rng(0).choice(n, k, replace=False)`` -- the same positions in every run and every build."""
+    import numpy as np
+    items = [(f"{k}.{k2}", t) for k, v in out.items() if isinstance(v, dict) for k2, t in v.items()]
+    items += [(k, v) for k, v in out.items() if not isinstance(v, dict)]
+    arrays, seen = {}, set()
+    for name, t in items:
+        if torch.is_tensor(t) and id(t) not in seen:
+            seen.add(id(t))
+            arrays[name] = t
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        k = share // a.itemsize
+        if a.size > k:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def default_view_group(world, views):
     """Ranks per view group of the hybrid latency mode: the largest divisor of ``world`` that is <= the number of source views
     (every rank of a group then owns at least one source view): 5 views -> N = 2: 2, 4: 4, 8: 4 (two groups)."""
@@ -594,9 +631,12 @@ def main():
         out = run_steps(args.steps)
         fence()
         dt = time.perf_counter() - t0
-    # latency modes: the same ranks also run as independent replicas (throughput mode) so that one line carries both
+    if args.dump_outputs and rank == 0:
+        with leg("dump_outputs"):
+            dump_outputs(out, args.dump_outputs)
+    # latency modes (--full): the same ranks also run as independent replicas (throughput mode) so that one line carries both
     dt_rep = None
-    if world > 1 and mode != "replicas":
+    if world > 1 and mode != "replicas" and args.full:
         with leg("replicas_pass"):
             group, shard_rows, grank, gworld = net.view_group, net.shard_rows, net.view_rank, net.view_world
             net.set_view_shard(None, 0, 1)
@@ -658,7 +698,7 @@ def main():
             net.set_view_shard(keep_shard[0], keep_shard[1], keep_shard[2], shard_rows=keep_shard[3])
         return (float(stat[1].item()) if dt_l is not None else None), comm_, float(stat[0].item())
 
-    if world > 1 and mode == "view-shard-rows":
+    if world > 1 and mode == "view-shard-rows" and args.full:
         with leg("latency_mode"):
             _, comm, rel_unsharded = latency_leg()
     split = None
@@ -682,7 +722,7 @@ def main():
     dt_full = None
     # everything the reference's forward returns (prob_volume [1,4,D,H,W] + depth_values [1,D,H,W] per stage); the H-slab path of the
     # view shard never forms prob_volume: the pass then runs unsharded, one depth map per rank
-    if (args.full_outputs or world == 1) and not args.no_full_outputs:
+    if args.full and (args.full_outputs or world == 1) and not args.no_full_outputs:
         with leg("full_outputs"):
             keep_shard = (net.view_group, net.view_rank, net.view_world, net.shard_rows)
             if net.shard_rows:
@@ -704,7 +744,7 @@ def main():
     # second pass of the same `steps` maps with HIP events around every kernel launch (roofline numbers); the
     # ~700 events per map cost ~4 % wall time, which is why this pass is not the one `value` comes from
     timer, dt_instr = None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         with leg("kernel_timing"):
             net.use_graph = False              # per-kernel HIP events need the individual launches
             net.feature_async_topdown = False  # and per-family busy times need FeatureNet off the stage-1 kernels' back
@@ -751,7 +791,8 @@ def main():
                 rccl_version = ".".join(map(str, torch.cuda.nccl.version()))
             except Exception:
                 rccl_version = "unknown"
-    dt, dt_rep = float(tmax[0].item()), float(tmax[1].item())
+    dt = float(tmax[0].item())
+    dt_rep = float(tmax[1].item()) if dt_rep is not None else None
     dt_full = float(tmax[2].item()) if dt_full is not None else None   # max over ranks, like dt
     maps = args.steps * n_groups
 
@@ -799,15 +840,17 @@ def main():
             res["view_group"] = vg
             res["latency_mode"] = {"value": n_groups * args.steps / dt, "unit": "depth-maps/s", "ms_per_map": 1e3 * dt / args.steps,
                                    "what": f"ONE depth map at a time per view group of {vg} ranks (" + res["config"]["parallelism"] + ")"}
-            res["throughput_mode"] = {"value": world * args.steps / dt_rep, "unit": "depth-maps/s",
-                                      "ms_per_step": 1e3 * dt_rep / args.steps,
-                                      "what": f"{world} independent replicas on the same ranks, no collective"}
+            if dt_rep is not None:
+                res["throughput_mode"] = {"value": world * args.steps / dt_rep, "unit": "depth-maps/s",
+                                          "ms_per_step": 1e3 * dt_rep / args.steps,
+                                          "what": f"{world} independent replicas on the same ranks, no collective"}
         if world > 1 and auto:
-            # the default line of a multi-GPU run: `value` is the replicas rate (throughput_mode repeats it), latency_mode is
-            # north_star's partition measured right behind it (mvsnet.py:131-146 summed over view shards)
+            # the default line of a multi-GPU run: `value` is the replicas rate (throughput_mode repeats it); with --full, latency_mode
+            # is north_star's partition measured right behind it (mvsnet.py:131-146 summed over view shards)
             res["view_group"] = vg
             res["throughput_mode"] = {"value": maps / dt, "unit": "depth-maps/s", "ms_per_step": 1e3 * dt / args.steps,
                                       "what": f"{world} independent replicas, no data-path collective (= `value`)"}
+        if world > 1 and auto and args.full:
             res["latency_mode"] = {"mode": "view-shard-rows", "view_group": vg, "view_groups": world // vg,
                                    "what": (f"{world // vg} view group(s) x {vg} ranks: ONE depth map per group at a time, its {cfg['V'] - 1} source views "
                                             f"sharded over the group ((v - 1) mod {vg}), reduce_scatter of the partial similarity volumes along H + halo "
@@ -937,7 +980,7 @@ def main():
                         res["warp_hbm_frac_coherent"] = coh["frac"]
             spans = timer_spans
             res["ms_per_stage"] = {k: v / args.steps for k, v in spans.items() if k != "end"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             with leg("cpu_baseline"):
                 res["cpu_baseline"], ref_out, (Hs, Ws) = cpu_baseline(cfg)
             # parity of THIS build on THIS box, in the line: the HIP path on the inputs the oracle just processed
@@ -947,7 +990,7 @@ def main():
             torch.cuda.synchronize()
             res["parity"] = parity_block(gpu_out, ref_out, len(cfg["ndepths"]), (Hs, Ws))
             del gpu_out
-        if world == 1 and not args.no_aten_gpu_baseline and affordable("aten_gpu_baseline"):
+        if world == 1 and args.full and not args.no_aten_gpu_baseline and affordable("aten_gpu_baseline"):
             del out
             torch.cuda.empty_cache()
             with leg("aten_gpu_baseline"):
@@ -972,7 +1015,7 @@ def main():
     # path has run over RCCL / xGMI before the driver's first multi-GPU node), rank 0 prints the line with `latency_mode.error` and
     # every rank leaves with exit code 0 through os._exit: no further collective, no destroy_process_group that could hang as well.
     lat_error = None
-    if world > 1 and auto:
+    if world > 1 and auto and args.full:
         import threading
         emit_lock = threading.Lock()
         state = {"done": False}

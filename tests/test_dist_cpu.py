@@ -299,5 +299,37 @@ def test_bench_contract_cli():
         assert [bench.default_view_group(n, 5) for n in (2, 4, 8)] == [2, 4, 4]
         assert [bench.default_view_group(n, 11) for n in (2, 4, 8)] == [2, 4, 8]
         assert bench.default_view_group(8, 3) == 2 and bench.default_view_group(6, 5) == 3 and bench.default_view_group(4, 2) == 1
+        # a plain run times only the headline; the context legs and the output dump are opt-in
+        assert a.full is False and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "outs"]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == "outs"
     finally:
         sys.argv = old
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: every tensor of the forward's output dict once (the top-level aliases of the last stage are
+    not written twice), float32 / float64 only, under 64 MB in all, and an oversized array sampled at the same positions
+    in every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(0)
+    big = torch.rand(1, 4, 2048, 2048, generator=g)
+    small = torch.rand(1, 32, 40, generator=g, dtype=torch.float64)
+    out = {"stage1": {"depth": small, "mask": small > 0.5}, "stage2": {"depth_sub_plus": big}}
+    out.update(out["stage2"])
+    names = bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    assert names == ["stage1.depth", "stage1.mask", "stage2.depth_sub_plus"]
+    assert sorted(os.listdir(tmp_path / "a")) == [n + ".npy" for n in names]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    d = np.load(tmp_path / "a" / "stage1.depth.npy")
+    assert d.dtype == np.float64 and np.array_equal(d, small.numpy())
+    m = np.load(tmp_path / "a" / "stage1.mask.npy")
+    assert m.dtype == np.float32 and np.array_equal(m, (small > 0.5).float().numpy())
+    s = np.load(tmp_path / "a" / "stage2.depth_sub_plus.npy")
+    assert s.dtype == np.float32 and 0 < s.size < big.numel() and np.isin(s, big.numpy()).all()
+    assert np.array_equal(s, np.load(tmp_path / "b" / "stage2.depth_sub_plus.npy"))

@@ -272,7 +272,7 @@ def test_bench_eight_ranks_view_shard_rows():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dist-backend", "gloo", "--share-gpu",
-           "--mode", "view-shard-rows", "--config", "c3_small", "--steps", "2", "--warmup", "1", "--no-kernel-timing"]
+           "--mode", "view-shard-rows", "--config", "c3_small", "--steps", "2", "--warmup", "1", "--no-kernel-timing", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=840)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -300,7 +300,7 @@ def test_bench_replicas_under_torchrun(world, config, vg):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-           "--dist-backend", "gloo", "--share-gpu", "--config", config] + (["--no-kernel-timing"] if world > 2 else [])
+           "--dist-backend", "gloo", "--share-gpu", "--config", config, "--full"] + (["--no-kernel-timing"] if world > 2 else [])
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1400)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -342,7 +342,7 @@ def test_bench_line_survives_a_failing_latency_leg(fault):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--dist-backend", "gloo", "--share-gpu", "--config", "c3_small", "--no-kernel-timing",
-           "--inject-latency-fault", fault, "--latency-budget-s", "25"]
+           "--inject-latency-fault", fault, "--latency-budget-s", "25", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
