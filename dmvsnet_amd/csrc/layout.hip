@@ -49,6 +49,103 @@ extern "C" int dmvs_nchw_to_hwc(const float* src, int c0, int C, int H, int W, f
     return dmvs_planar_to_hwc(src, (long)H * W, c0, C, H, W, dst, s);
 }
 
+// ------------------------------------------------------------------ image ingest
+// Decoded image -> the [3][H][W] fp32 planes FeatureNet reads, bit-identical to the eval loader (eval_io.MVSDataset):
+// uint8 -> float through the host's 256-entry table (np.float32(u) / 255.0), then eval_io.resize_linear's two passes
+// with the host's tap tables: row r = a*(1-fx) + b*fx for the rows y0 and y1, then out = r0*(1-fy) + r1*fy -- each a
+// separate fp32 multiply / multiply / add (the library builds with -ffp-contract=off).  A thread owns 4 consecutive
+// output pixels of one row and recomputes both source rows in registers (no intermediate buffer).
+template <bool U8>
+__device__ __forceinline__ float ingest_px(const void* src, const float* lut, int w, int y, int x, int c) {
+    const size_t i = ((size_t)y * w + x) * 3 + c;
+    if (U8) return lut[((const unsigned char*)src)[i]];
+    return ((const float*)src)[i];
+}
+
+template <bool U8, bool RESIZE>
+__global__ __launch_bounds__(256) void image_ingest_kernel(const void* __restrict__ src, int h, int w,
+                                                           const float* __restrict__ lut,
+                                                           const int* __restrict__ tx_idx, const float* __restrict__ tx_wt,
+                                                           const int* __restrict__ ty_idx, const float* __restrict__ ty_wt,
+                                                           int H, int W, float* __restrict__ dst, int out_hwc, int vec) {
+    const int y = blockIdx.y;
+    const int x0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (x0 >= W) return;
+    float v[3][4];
+    int ya = y, yb = y;
+    float wya = 1.f, wyb = 0.f;
+    if (RESIZE) {
+        ya = min(max(ty_idx[y], 0), h - 1);
+        yb = min(max(ty_idx[H + y], 0), h - 1);
+        wya = ty_wt[y];
+        wyb = ty_wt[H + y];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = min(x0 + k, W - 1);   // lanes past the row end compute a duplicate, never stored
+        if (!RESIZE) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][k] = ingest_px<U8>(src, lut, w, y, x, c);
+            continue;
+        }
+        const int xa = min(max(tx_idx[x], 0), w - 1), xb = min(max(tx_idx[W + x], 0), w - 1);
+        const float wxa = tx_wt[x], wxb = tx_wt[W + x];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float ra = ingest_px<U8>(src, lut, w, ya, xa, c) * wxa + ingest_px<U8>(src, lut, w, ya, xb, c) * wxb;
+            const float rb = ingest_px<U8>(src, lut, w, yb, xa, c) * wxa + ingest_px<U8>(src, lut, w, yb, xb, c) * wxb;
+            v[c][k] = ra * wya + rb * wyb;
+        }
+    }
+    const size_t HW = (size_t)H * W;
+    if (vec) {   // W % 4 == 0 and a 16-byte aligned destination: whole quads, 16-byte stores
+        if (out_hwc) {
+            float4_t* o = (float4_t*)(dst + ((size_t)y * W + x0) * 3);
+            o[0] = float4_t{v[0][0], v[1][0], v[2][0], v[0][1]};
+            o[1] = float4_t{v[1][1], v[2][1], v[0][2], v[1][2]};
+            o[2] = float4_t{v[2][2], v[0][3], v[1][3], v[2][3]};
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                *(float4_t*)(dst + c * HW + (size_t)y * W + x0) = float4_t{v[c][0], v[c][1], v[c][2], v[c][3]};
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = x0 + k;
+        if (x >= W) break;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (out_hwc) dst[((size_t)y * W + x) * 3 + c] = v[c][k];
+            else dst[c * HW + (size_t)y * W + x] = v[c][k];
+        }
+    }
+}
+
+extern "C" int dmvs_image_ingest(const void* src, int src_u8, int h, int w, const float* lut256, const int* tx_idx,
+                                 const float* tx_wt, const int* ty_idx, const float* ty_wt, int H, int W, float* dst,
+                                 int out_hwc, dmvs_stream_t s) {
+    if (!src || !dst || h <= 0 || w <= 0 || H <= 0 || W <= 0 || (src_u8 && !lut256)) return DMVS_EINVAL;
+    const bool resize = (h != H || w != W);
+    if (resize && (!tx_idx || !tx_wt || !ty_idx || !ty_wt)) return DMVS_EINVAL;
+    const int vec = (W % 4 == 0 && ((uintptr_t)dst & 15) == 0) ? 1 : 0;
+    dim3 grid(ceil_div(ceil_div(W, 4), 256), H);
+    hipStream_t st = (hipStream_t)s;
+    if (src_u8) {
+        if (resize)
+            image_ingest_kernel<true, true><<<grid, 256, 0, st>>>(src, h, w, lut256, tx_idx, tx_wt, ty_idx, ty_wt, H, W, dst, out_hwc, vec);
+        else
+            image_ingest_kernel<true, false><<<grid, 256, 0, st>>>(src, h, w, lut256, tx_idx, tx_wt, ty_idx, ty_wt, H, W, dst, out_hwc, vec);
+    } else {
+        if (resize)
+            image_ingest_kernel<false, true><<<grid, 256, 0, st>>>(src, h, w, lut256, tx_idx, tx_wt, ty_idx, ty_wt, H, W, dst, out_hwc, vec);
+        else
+            image_ingest_kernel<false, false><<<grid, 256, 0, st>>>(src, h, w, lut256, tx_idx, tx_wt, ty_idx, ty_wt, H, W, dst, out_hwc, vec);
+    }
+    DMVS_LAUNCH_CHECK();
+}
+
 // ------------------------------------------------------------------ relative projections
 // One thread per source view.  Composition K*E is fp32 (as mvsnet.py:134,136); the 4x4 inverse and
 // the product are done in fp64 with partial pivoting and rounded once to fp32.  torch.inverse is an

@@ -78,6 +78,23 @@ def write_cam(file, cam):
 
 
 # ------------------------------------------------------------------------------------------ dataset
+def resize_taps(n_out: int, n_in: int):
+    """Tap table of one axis of ``resize_linear``: (i0, i1) int64 source indices and the fp32 weight ``f`` of i1 per output
+    index (half-pixel centres, edge replication).  Also what the GPU ingest kernel reads (scan.py, dmvs_image_ingest)."""
+    f = ((np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5).astype(np.float32)
+    i0 = np.floor(f).astype(np.int64)
+    f = f - i0.astype(np.float32)
+    lo, hi = i0 < 0, i0 >= n_in - 1
+    f[lo | hi] = 0.0
+    i0 = np.clip(i0, 0, n_in - 1)
+    return i0, np.minimum(i0 + 1, n_in - 1), f
+
+
+def u8_to_float_table() -> np.ndarray:
+    """[256] fp32: the loader's ``np.array(img, dtype=np.float32) / 255.0`` for every uint8 value (MVSDataset._view)."""
+    return np.arange(256, dtype=np.float32) / 255.0
+
+
 def resize_linear(img: np.ndarray, new_h: int, new_w: int) -> np.ndarray:
     """``cv2.resize(img, (new_w, new_h))`` (INTER_LINEAR, the default) for float32 images, restated from OpenCV's
     published algorithm (resizeGeneric / HResizeLinear + VResizeLinear): half-pixel centres
@@ -89,13 +106,7 @@ def resize_linear(img: np.ndarray, new_h: int, new_w: int) -> np.ndarray:
         return img
 
     def taps(n_out, n_in):
-        f = ((np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5).astype(np.float32)
-        i0 = np.floor(f).astype(np.int64)
-        f = f - i0.astype(np.float32)
-        lo, hi = i0 < 0, i0 >= n_in - 1
-        f[lo | hi] = 0.0
-        i0 = np.clip(i0, 0, n_in - 1)
-        return torch.from_numpy(i0), torch.from_numpy(np.minimum(i0 + 1, n_in - 1)), torch.from_numpy(f)
+        return tuple(torch.from_numpy(a) for a in resize_taps(n_out, n_in))
 
     t = torch.from_numpy(np.ascontiguousarray(img, dtype=np.float32))
     squeeze = t.dim() == 2
@@ -161,10 +172,25 @@ class ResizePolicy:
         """Resize ``img`` to ``size`` (default: the policy's target) and scale the intrinsics' rows with it."""
         h, w = img.shape[:2]
         new_h, new_w = self.target(h, w) if size is None else size
-        K = intrinsics.copy()
-        K[0, :] *= 1.0 * new_w / w
-        K[1, :] *= 1.0 * new_h / h
-        return resize_linear(img, new_h, new_w), K
+        return resize_linear(img, new_h, new_w), scale_intrinsics(intrinsics, (h, w), (new_h, new_w))
+
+
+def scale_intrinsics(intrinsics: np.ndarray, size, new_size) -> np.ndarray:
+    """A copy of ``intrinsics`` with its x / y rows scaled from image size (h, w) to (new_h, new_w) (general_eval.py:105-106)."""
+    (h, w), (new_h, new_w) = size, new_size
+    K = intrinsics.copy()
+    K[0, :] *= 1.0 * new_w / w
+    K[1, :] *= 1.0 * new_h / h
+    return K
+
+
+def stage_proj_matrices(proj_matrices: np.ndarray) -> Dict[str, np.ndarray]:
+    """[V,2,4,4] (stage-1 intrinsics) -> {"stage1|2|3": intrinsics x1, x2, x4} (general_eval.py:189-198)."""
+    ms = {}
+    for k, mul in (("stage1", 1), ("stage2", 2), ("stage3", 4)):
+        ms[k] = proj_matrices.copy()
+        ms[k][:, 1, :2, :] = proj_matrices[:, 1, :2, :] * mul
+    return ms
 
 
 def read_pairs(filename, nviews: Optional[int] = None):
@@ -241,11 +267,7 @@ class MVSDataset(torch.utils.data.Dataset):
             proj_mat = np.zeros((2, 4, 4), dtype=np.float32)
             proj_mat[0], proj_mat[1, :3, :3] = E, K
             proj_matrices.append(proj_mat)
-        proj_matrices = np.stack(proj_matrices)
-        ms = {}
-        for k, mul in (("stage1", 1), ("stage2", 2), ("stage3", 4)):
-            ms[k] = proj_matrices.copy()
-            ms[k][:, 1, :2, :] = proj_matrices[:, 1, :2, :] * mul
+        ms = stage_proj_matrices(np.stack(proj_matrices))
         return {"imgs": np.stack(imgs).transpose([0, 3, 1, 2]), "proj_matrices": ms, "depth_values": depth_values,
                 "filename": scan + "/{}/" + "{:0>8}".format(view_ids[0]) + "{}"}
 
@@ -254,11 +276,21 @@ class MVSDataset(torch.utils.data.Dataset):
 @torch.no_grad()
 def save_depth_maps(network, datapath: str, testlist: Sequence[str], outdir: str, num_view: int, max_h: int, max_w: int,
                     numdepth: int = 192, interval_scale: float = 1.06, inverse_depth: bool = False, device="cuda",
-                    write_images: bool = True, fix_res: bool = False, scene_cfg: Optional[Dict[str, dict]] = None) -> List[str]:
+                    write_images: bool = True, fix_res: bool = False, scene_cfg: Optional[Dict[str, dict]] = None,
+                    feature_cache=None, stats: Optional[dict] = None) -> List[str]:
     """Step 1 of Model.test (model.py:323-380): run ``network`` on every reference view of every scene and write
     ``<outdir>/<scan>/depth_est/%08d.pfm``, ``confidence/%08d.pfm``, ``cams/%08d_cam.txt`` (and ``images/%08d.jpg``).
     ``scene_cfg``: optional per-scene overrides ``{scene: {"max_h": .., "max_w": ..}}`` -- the reference's ``tank_cfg``
-    table (model.py:325-328).  ``fix_res``: main.py's ``--fix_res``.  Returns the list of depth files written."""
+    table (model.py:325-328).  ``fix_res``: main.py's ``--fix_res``.  Returns the list of depth files written.
+    ``feature_cache`` (EXTENSION, opt-in): ``True`` (default byte budget) or a byte budget runs the scan-level path
+    (scan.save_depth_maps_cached): every image decoded, ingested on the GPU and run through FeatureNet once per scan, each
+    depth map from cached features -- the same files with the same bytes.  ``stats``: a dict that path fills with its
+    cache counters and phase times.  None / False: the per-sample loader path below."""
+    if feature_cache is not None and feature_cache is not False:
+        from . import scan
+        return scan.save_depth_maps_cached(network, datapath, testlist, outdir, num_view, max_h, max_w, numdepth,
+                                           interval_scale, inverse_depth, device, write_images, fix_res, scene_cfg,
+                                           max_bytes=None if feature_cache is True else int(feature_cache), stats=stats)
     network.eval()
     num_stage = len(network.ndepths)
     written = []
@@ -295,7 +327,8 @@ def run_test(network, datapath: str, testlist: Sequence[str], outdir: str, num_v
              numdepth: int = 192, interval_scale: float = 1.06, inverse_depth: bool = False, conf=(0.1, 0.15, 0.7),
              thres_view: int = 5, filter_method: str = "pcd", device="cuda", fix_res: bool = False,
              dist_base: float = 1 / 4, rel_diff_base: float = 1 / 1300,
-             scene_cfg: Optional[Dict[str, dict]] = None) -> Dict[str, Dict[str, float]]:
+             scene_cfg: Optional[Dict[str, dict]] = None, feature_cache=None,
+             stats: Optional[dict] = None) -> Dict[str, Dict[str, float]]:
     """Both steps of ``Model.test`` (model.py:297-390): depth / confidence maps of every reference view, then the
     fusion filter per scene -- ``filter_method`` "pcd" (filter/pcd.py) or "dypcd" (the dynamic-threshold variant,
     filter/dypcd_tanks.py) -- into ``<outdir>/pcd/<name>.ply`` (``mvsnet%03d_l3.ply`` for DTU ``scanN`` names,
@@ -304,10 +337,11 @@ def run_test(network, datapath: str, testlist: Sequence[str], outdir: str, num_v
     final ``confidence.pfm`` (model.py:372-375), so -- exactly as in the reference -- all three thresholds are applied to
     that one map and the effective photometric gate is its largest value (0.7 by default).  ``scene_cfg``: per-scene
     overrides ``{scene: {"max_h", "max_w", "conf"}}`` (the reference's ``tank_cfg``: model.py:325-328, pcd.py:375-377).
+    ``feature_cache`` / ``stats``: step 1 on the scan-level path (see ``save_depth_maps``).
     Returns the mask statistics of the last reference view per scene."""
     from . import fusion
     save_depth_maps(network, datapath, testlist, outdir, num_view, max_h, max_w, numdepth, interval_scale, inverse_depth,
-                    device, fix_res=fix_res, scene_cfg=scene_cfg)
+                    device, fix_res=fix_res, scene_cfg=scene_cfg, feature_cache=feature_cache, stats=stats)
     os.makedirs(os.path.join(outdir, "pcd"), exist_ok=True)
     stats = {}
     for scan in testlist:

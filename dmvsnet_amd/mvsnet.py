@@ -738,19 +738,14 @@ class MVSNet(nn.Module):
         ops.mark("features")
         views = [0] + local
         batch = imgs[0] if len(views) == V else imgs[0, views]
-        # view groups: a [32][g][H][W] activation must stay below the 2 GB range of a buffer descriptor
-        gmax = self.feature_group_views or max(1, ((1 << 29) - 1) // (32 * H * W))
+        gmax = self._feature_group_max(H, W)
         groups = [list(range(i, min(i + gmax, len(views)))) for i in range(0, len(views), gmax)]
         side = self._side_stream(imgs.device, "fpn") if (self.feature_async_topdown and len(groups) == 1) else None
         self.feature._topdown_done = None
         # relative projections of every stage first: they depend on the cameras only, and a kernel launched between K4 of one
         # stage and K1 of the next would sit in the dependent chain (every kernel boundary is a cache write-back + a dispatch
         # gap of several microseconds on this multi-XCD GPU)
-        # a loader that emits only the reference's three projection scales (general_eval.py:189-198) serves a deeper
-        # pyramid BY LEVEL; one written for the extension carries an entry per stage ("stage1" .. "stageS")
-        per_stage = self.num_stage <= 3 or "stage{}".format(self.num_stage) in proj_matrices
-        pkeys = ["stage{}".format((s if per_stage else self.stage_level(s)) + 1) for s in range(self.num_stage)]
-        proj_rel = {k: ops.relative_proj(proj_matrices[k][0].contiguous()) for k in dict.fromkeys(pkeys)}   # [V-1,12] each
+        pkeys, proj_rel = self._relative_projections(proj_matrices)
         stacks = [self.feature.run(batch[g[0]:g[-1] + 1].contiguous(), side) for g in groups]   # each: 3 x [2, g, C/4, h, w, 4]
         if self.feature_dtype == "f16":
             if W % 8:
@@ -762,8 +757,28 @@ class MVSNet(nn.Module):
         elif self.feature_dtype != "f32":
             raise DmvsError(f"feature_dtype must be 'f32' or 'f16', not {self.feature_dtype!r}")
         slot = {v: (gi, k) for gi, g in enumerate(groups) for k, i in enumerate(g) for v in [views[i]]}
-        reg_side = self._side_stream(imgs.device, "reg") if self.two_streams else None
 
+        def half(v, c0, level):
+            return stacks[slot[v][0]][level][1 if c0 else 0, slot[v][1]]   # [C/4, h, w, 4], contiguous
+
+        return self._stages(half, V, H, W, local, rows, proj_rel, pkeys, depth_values, imgs.device)
+
+    def _feature_group_max(self, H, W):
+        """Views per FeatureNet call: a [32][g][H][W] activation must stay below the 2 GB range of a buffer descriptor."""
+        return self.feature_group_views or max(1, ((1 << 29) - 1) // (32 * H * W))
+
+    def _relative_projections(self, proj_matrices):
+        """-> (projection key of every stage, {key: [V-1,12] relative projections}).  A loader that emits only the
+        reference's three projection scales (general_eval.py:189-198) serves a deeper pyramid BY LEVEL; one written for the
+        extension carries an entry per stage ("stage1" .. "stageS")."""
+        per_stage = self.num_stage <= 3 or "stage{}".format(self.num_stage) in proj_matrices
+        pkeys = ["stage{}".format((s if per_stage else self.stage_level(s)) + 1) for s in range(self.num_stage)]
+        return pkeys, {k: ops.relative_proj(proj_matrices[k][0].contiguous()) for k in dict.fromkeys(pkeys)}
+
+    def _stages(self, half, V, H, W, local, rows, proj_rel, pkeys, depth_values, device):
+        """The stage loop (mvsnet.py:208-258) on features looked up by ``half(v, c0, level)`` -> [C/4, h, w, 4] of view v
+        (0 = reference), channel half c0 (0: stageK, 1: stageK_c) at FPN level ``level``."""
+        reg_side = self._side_stream(device, "reg") if self.two_streams else None
         outputs = {}
         last_depth = None
         last_level = 0
@@ -788,19 +803,19 @@ class MVSNet(nn.Module):
             proj12 = proj_all[[v - 1 for v in local]].contiguous() if len(local) != V - 1 else proj_all
             C = self.feature.out_channels[level]
 
-            def half(v, c0, level=level):
-                return stacks[slot[v][0]][level][1 if c0 else 0, slot[v][1]]   # [C/4, h, w, 4], contiguous
+            def half_s(v, c0, level=level):
+                return half(v, c0, level)
 
             if rows:
-                out_main, out_ref = self._stage_rows(s, half, local, proj12, hyp, interval, C, reg_side)
+                out_main, out_ref = self._stage_rows(s, half_s, local, proj12, hyp, interval, C, reg_side)
             else:
-                sim = self.cost_aggregation.forward(half(0, 0), [half(v, 0) for v in local], proj12, hyp, self.view_group)
+                sim = self.cost_aggregation.forward(half_s(0, 0), [half_s(v, 0) for v in local], proj12, hyp, self.view_group)
                 fuse = not self.return_prob_volume and ops.prob_fusable(D, w, self.conv_backend)
                 cost_reg = self.cost_regularization[s].run(sim, self.conv_backend, reg_side, (hyp, interval, 1.0) if fuse else None)
                 out_main = self.DepthNet.forward(cost_reg, hyp, interval, self.return_prob_volume, self.return_depth_values)
 
                 hyp_c = out_main["depth_values_c"][0]
-                sim_c = self.cost_aggregation.forward(half(0, C), [half(v, C) for v in local], proj12, hyp_c,
+                sim_c = self.cost_aggregation.forward(half_s(0, C), [half_s(v, C) for v in local], proj12, hyp_c,
                                                       self.view_group)
                 fuse_c = ops.prob_fusable(4, w, self.conv_backend)
                 cost_reg_c = self.cost_regularization_refine[s].run(sim_c, self.conv_backend, reg_side, (hyp_c, interval, 5.0) if fuse_c else None)
@@ -812,3 +827,72 @@ class MVSNet(nn.Module):
             outputs.update(outputs_stage)
         ops.mark("end")
         return outputs
+
+    # -- scan level: encode once, forward from features ----------------------------------------------
+    @torch.no_grad()
+    def encode_views(self, imgs_v: torch.Tensor) -> List["ViewFeatures"]:
+        """imgs_v [n,3,H,W] (any n) -> one ``ViewFeatures`` per image: FeatureNet in groups of at most the descriptor-bound
+        group size, on the current stream (no side stream), cast to ``feature_dtype``.  Each image's three levels x two
+        channel halves are copied out of the group's output into tensors of its own, so that dropping one image's
+        ``ViewFeatures`` frees exactly its ``nbytes``."""
+        if not imgs_v.is_cuda:
+            raise DmvsError("encode_views runs on a HIP device only (no CPU fallback)")
+        if self.feature_dtype not in ("f32", "f16"):
+            raise DmvsError(f"feature_dtype must be 'f32' or 'f16', not {self.feature_dtype!r}")
+        n, _, H, W = imgs_v.shape
+        if self.feature_dtype == "f16" and W % 8:
+            raise DmvsError("feature_dtype='f16' needs an image width that is a multiple of 8 (pixel pairs at 1/4 scale)")
+        self.prepare(imgs_v.device)
+        fp = self._fingerprint(imgs_v.device)
+        gmax = self._feature_group_max(H, W)
+        out = []
+        for g0 in range(0, n, gmax):
+            self.feature._topdown_done = None
+            stack = self.feature.run(imgs_v[g0:g0 + gmax].contiguous(), None)   # 3 x [2, g, C/4, h, w, 4]
+            for k in range(stack[0].shape[1]):
+                levels = tuple(o[:, k].to(torch.float16 if self.feature_dtype == "f16" else torch.float32,
+                                          memory_format=torch.contiguous_format, copy=True) for o in stack)
+                out.append(ViewFeatures(levels, (H, W), self.feature_dtype, sum(t.numel() * t.element_size() for t in levels), fp))
+        return out
+
+    @torch.no_grad()
+    def forward_features(self, views: Sequence["ViewFeatures"], proj_matrices, depth_values):
+        """``forward`` from cached features: ``views[0]`` is the reference view, the rest its source views in the order of
+        ``proj_matrices`` ({"stageK": [1,V,2,4,4]}) and ``depth_values`` [1,n].  Same output keys and the same bits as
+        ``forward`` on the images the views were encoded from (FeatureNet's output does not depend on the view grouping).
+        Eager only (``use_graph`` does not apply), one depth map (batch 1), no view group / row sharding."""
+        if self.view_group is not None or self.shard_rows:
+            raise DmvsError("forward_features is not combined with view or row sharding")
+        if depth_values.dim() != 2 or depth_values.shape[0] != 1 or any(v.shape[0] != 1 for v in proj_matrices.values()):
+            raise DmvsError("forward_features runs one depth map (batch 1)")
+        V = len(views)
+        if V < 2 or any(v.shape[1] != V for v in proj_matrices.values()):
+            raise DmvsError(f"forward_features: {V} views but proj_matrices of shape {tuple(next(iter(proj_matrices.values())).shape)}")
+        device = depth_values.device
+        if not depth_values.is_cuda:
+            raise DmvsError("forward_features runs on a HIP device only (no CPU fallback)")
+        self.prepare(device)
+        fp = self._fingerprint(device)
+        if any(v.fingerprint != fp for v in views):
+            raise DmvsError("forward_features: a ViewFeatures was encoded with other weights (or on another device); re-encode it")
+        if len({(v.size, v.dtype) for v in views}) != 1:
+            raise DmvsError("forward_features: views of different sizes or feature dtypes: "
+                            f"{sorted({(v.size, v.dtype) for v in views})}")
+        H, W = views[0].size
+        self.feature._topdown_done = None
+        pkeys, proj_rel = self._relative_projections(proj_matrices)
+
+        def half(v, c0, level):
+            return views[v].levels[level][1 if c0 else 0]   # [C/4, h, w, 4], contiguous
+
+        return self._stages(half, V, H, W, list(range(1, V)), False, proj_rel, pkeys, depth_values.contiguous(), device)
+
+
+class ViewFeatures:
+    """FeatureNet's output for one image (MVSNet.encode_views): ``levels`` = three [2, C/4, h, w, 4] tensors (stageK /
+    stageK_c halves, quad-planar) from the coarsest level to full resolution; ``size`` the image's (H, W); ``dtype``
+    "f32" | "f16"; ``nbytes`` the bytes the tensors own; ``fingerprint`` the weights they were made with (MVSNet._fingerprint)."""
+    __slots__ = ("levels", "size", "dtype", "nbytes", "fingerprint")
+
+    def __init__(self, levels, size, dtype, nbytes, fingerprint):
+        self.levels, self.size, self.dtype, self.nbytes, self.fingerprint = levels, tuple(size), dtype, nbytes, fingerprint

@@ -163,6 +163,40 @@ def planar_to_hwc(stack: torch.Tensor, view: int, c0: int, C: int) -> torch.Tens
     return dst
 
 
+def image_ingest(src: torch.Tensor, H: int, W: int, lut: Optional[torch.Tensor] = None, taps=None,
+                 out: Optional[torch.Tensor] = None, hwc: bool = False) -> torch.Tensor:
+    """Decoded image src [h,w,3] (uint8 with ``lut`` [256] fp32, or fp32) -> [3,H,W] planes (``hwc``: [H,W,3]) in ``out``
+    (e.g. one slot of a [n,3,H,W] FeatureNet input stack; allocated if None).  ``taps`` = (tx_idx [2,W] int32, tx_wt [2,W],
+    ty_idx [2,H] int32, ty_wt [2,H]) device tables of eval_io.resize_taps; unused when (h, w) == (H, W).  Layout glue: the
+    launch is not logged."""
+    if not src.is_cuda or not src.is_contiguous() or src.dim() != 3 or src.shape[2] != 3:
+        raise _lib.DmvsError(f"image_ingest: src must be a contiguous [h,w,3] HIP tensor, got {tuple(src.shape)} on {src.device}")
+    u8 = src.dtype == torch.uint8
+    if not u8 and src.dtype != torch.float32:
+        raise _lib.DmvsError(f"image_ingest: src must be uint8 or float32, not {src.dtype}")
+    if u8:
+        _req(lut)
+        assert lut.numel() == 256
+    h, w = src.shape[:2]
+    shape = (H, W, 3) if hwc else (3, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    _req(out)
+    assert tuple(out.shape) == shape, (tuple(out.shape), shape)
+    tx_i = tx_w = ty_i = ty_w = None
+    if (h, w) != (H, W):
+        tx_i, tx_w, ty_i, ty_w = taps
+        _req(tx_w, ty_w)
+        for t, n in ((tx_i, W), (ty_i, H)):
+            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (2, n)):
+                raise _lib.DmvsError("image_ingest: tap indices must be contiguous [2,n] int32 HIP tensors")
+        assert tuple(tx_w.shape) == (2, W) and tuple(ty_w.shape) == (2, H)
+    _lib.check(_lib.load().dmvs_image_ingest(_ptr(src), int(u8), h, w, _ptr(lut) if u8 else None, _ptr(tx_i), _ptr(tx_w),
+                                             _ptr(ty_i), _ptr(ty_w), H, W, _ptr(out), int(hwc), _stream()),
+               "dmvs_image_ingest")
+    return out
+
+
 def relative_proj(proj_pairs: torch.Tensor) -> torch.Tensor:
     """proj_pairs [V,2,4,4] -> [V-1,12] (rot 9 + trans 3 of src @ inv(ref))."""
     _req(proj_pairs)

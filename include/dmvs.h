@@ -89,6 +89,19 @@ int dmvs_nchw_to_hwc(const float* src_chw, int c0, int C, int H, int W, float* d
 int dmvs_planar_to_hwc(const float* src, long chan_stride, int c0, int C, int H, int W, float* dst_hwc,
                        dmvs_stream_t stream);
 
+/* Image ingest of the scan-level eval path: one decoded image -> the [3][H][W] fp32 planes FeatureNet reads, bit-identical
+ * to the eval loader's host work it replaces (eval_io.MVSDataset: PIL decode / 255, eval_io.ResizePolicy.apply ->
+ * eval_io.resize_linear; the reference's general_eval.py:97-110 + cv2.resize).  Layout glue: not a logged kernel.
+ *   src         [h][w][3] uint8 (src_u8 = 1; converted through lut256, the host's np.float32(u) / 255.0) or fp32
+ *   tx_idx/wt   [2][W]: source columns (i0, i1) and weights (1 - f, f) of eval_io.resize_taps(W, w); ty_* the same [2][H]
+ *               for rows.  Ignored (may be NULL) when (h, w) == (H, W): the identity, as in resize_linear.
+ *   dst         [3][H][W] planes (out_hwc = 0; e.g. one slot of a [V][3][H][W] FeatureNet input stack) or [H][W][3]
+ *               fp32 (out_hwc = 1: the first pass of a chained resize).
+ * Per output value: r_k = a_k*(1-fx) + b_k*fx for the source rows y0, y1, then r_0*(1-fy) + r_1*fy, unfused fp32. */
+int dmvs_image_ingest(const void* src, int src_u8, int h, int w, const float* lut256, const int* tx_idx,
+                      const float* tx_wt, const int* ty_idx, const float* ty_wt, int H, int W, float* dst, int out_hwc,
+                      dmvs_stream_t stream);
+
 /* Relative projections for all source views of one stage.
  * proj_pairs [V][2][4][4] (view 0 = reference): [v][0] extrinsic, [v][1][:3][:3] intrinsics.
  * out [V-1][12]: rot (row-major 3x3) then trans (3) of  (K_s E_s) (K_r E_r)^-1.
