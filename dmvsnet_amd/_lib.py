@@ -67,6 +67,9 @@ SIGNATURES = {
     "dmvs_pack_conv_weights_mfma": (_i, [_p, _p, _i, _i, _i, _i]),
     "dmvs_geo_consistency": (_i, [_p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
     "dmvs_geo_consistency_ladder": (_i, [_p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p]),
+    "dmvs_fuse_workgroups": (ctypes.c_long, [_i, _i]),
+    "dmvs_fuse_view": (_i, [_p, _p, _p, _p, _i, _i, _i, ctypes.POINTER(_p), _p, _f, _f, _f, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
+    "dmvs_fuse_emit": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "dmvs_prob_regress": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p]),
     "dmvs_depth_select": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "dmvs_depth_regress": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

@@ -328,7 +328,7 @@ def run_test(network, datapath: str, testlist: Sequence[str], outdir: str, num_v
              thres_view: int = 5, filter_method: str = "pcd", device="cuda", fix_res: bool = False,
              dist_base: float = 1 / 4, rel_diff_base: float = 1 / 1300,
              scene_cfg: Optional[Dict[str, dict]] = None, feature_cache=None,
-             stats: Optional[dict] = None) -> Dict[str, Dict[str, float]]:
+             stats: Optional[dict] = None, resident_fusion: bool = False) -> Dict[str, Dict[str, float]]:
     """Both steps of ``Model.test`` (model.py:297-390): depth / confidence maps of every reference view, then the
     fusion filter per scene -- ``filter_method`` "pcd" (filter/pcd.py) or "dypcd" (the dynamic-threshold variant,
     filter/dypcd_tanks.py) -- into ``<outdir>/pcd/<name>.ply`` (``mvsnet%03d_l3.ply`` for DTU ``scanN`` names,
@@ -338,18 +338,47 @@ def run_test(network, datapath: str, testlist: Sequence[str], outdir: str, num_v
     that one map and the effective photometric gate is its largest value (0.7 by default).  ``scene_cfg``: per-scene
     overrides ``{scene: {"max_h", "max_w", "conf"}}`` (the reference's ``tank_cfg``: model.py:325-328, pcd.py:375-377).
     ``feature_cache`` / ``stats``: step 1 on the scan-level path (see ``save_depth_maps``).
+    ``resident_fusion`` (EXTENSION, opt-in, needs ``feature_cache``): step 2 on the same path -- every map is fused on the
+    device as soon as its view's sources are there (``fusion.ScanFusion``), without the file round trip; the same files
+    (mask PNGs: the same pixels) and the same return value.
     Returns the mask statistics of the last reference view per scene."""
     from . import fusion
+
+    def ply_path(scan):
+        name = "mvsnet{:0>3}_l3.ply".format(int(scan[4:])) if scan.startswith("scan") and scan[4:].isdigit() else "{}.ply".format(scan)
+        return os.path.join(outdir, "pcd", name)
+
+    def fusion_args(scan):
+        sc = (scene_cfg or {}).get(scan, {})
+        return (fusion.read_pair_file(os.path.join(datapath, scan, "pair.txt")),
+                dict(conf=sc.get("conf", conf), thres_view=thres_view, dynamic=filter_method == "dypcd",
+                     num_stage=len(network.ndepths), device=device, dist_base=dist_base, rel_diff_base=rel_diff_base))
+
+    if resident_fusion:
+        if feature_cache is None or feature_cache is False:
+            from ._lib import DmvsError
+            raise DmvsError("resident_fusion runs on the scan-level path: pass feature_cache=True (or a byte budget)")
+        from . import scan as scan_mod
+        os.makedirs(os.path.join(outdir, "pcd"), exist_ok=True)
+        out = {}
+
+        def begin(scan):
+            pairs, kw = fusion_args(scan)
+            return fusion.ScanFusion(pairs, **kw)
+
+        def end(scan, fz):
+            out[scan] = fz.write(os.path.join(outdir, scan), ply_path(scan))
+
+        scan_mod.save_depth_maps_cached(network, datapath, testlist, outdir, num_view, max_h, max_w, numdepth,
+                                        interval_scale, inverse_depth, device, True, fix_res, scene_cfg,
+                                        max_bytes=None if feature_cache is True else int(feature_cache), stats=stats,
+                                        fusion=(begin, end))
+        return out
     save_depth_maps(network, datapath, testlist, outdir, num_view, max_h, max_w, numdepth, interval_scale, inverse_depth,
                     device, fix_res=fix_res, scene_cfg=scene_cfg, feature_cache=feature_cache, stats=stats)
     os.makedirs(os.path.join(outdir, "pcd"), exist_ok=True)
     stats = {}
     for scan in testlist:
-        name = "mvsnet{:0>3}_l3.ply".format(int(scan[4:])) if scan.startswith("scan") and scan[4:].isdigit() else "{}.ply".format(scan)
-        pairs = fusion.read_pair_file(os.path.join(datapath, scan, "pair.txt"))
-        sc = (scene_cfg or {}).get(scan, {})
-        stats[scan] = fusion.fuse_scene(pairs, os.path.join(outdir, scan), os.path.join(outdir, "pcd", name),
-                                        conf=sc.get("conf", conf), thres_view=thres_view, dynamic=filter_method == "dypcd",
-                                        num_stage=len(network.ndepths), device=device, dist_base=dist_base,
-                                        rel_diff_base=rel_diff_base)
+        pairs, kw = fusion_args(scan)
+        stats[scan] = fusion.fuse_scene(pairs, os.path.join(outdir, scan), ply_path(scan), **kw)
     return stats

@@ -11,12 +11,13 @@
 """
 from __future__ import annotations
 
+import io
 import os
 import queue
 import threading
 import time
 from collections import OrderedDict
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import Future, ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -249,16 +250,22 @@ def save_depth_maps_cached(network, datapath: str, testlist: Sequence[str], outd
                            max_w: int, numdepth: int = 192, interval_scale: float = 1.06, inverse_depth: bool = False,
                            device="cuda", write_images: bool = True, fix_res: bool = False,
                            scene_cfg: Optional[Dict[str, dict]] = None, max_bytes: Optional[int] = None,
-                           stats: Optional[dict] = None, workers: int = DECODE_WORKERS) -> List[str]:
+                           stats: Optional[dict] = None, workers: int = DECODE_WORKERS, fusion=None) -> List[str]:
     """``eval_io.save_depth_maps`` on the scan-level path: same arguments, same files with the same bytes, same return value.
     ``max_bytes``: feature-cache budget (None: ``default_budget()``).  ``stats`` (a dict, filled in): maps, images (distinct
     (view, resize chain) pairs), encodes / hits / misses / evictions / peak_bytes of the cache, budget, and with it the
-    seconds of each phase (decode, h2d_ingest, encode, forward, d2h, write; device phases from events) and wall."""
+    seconds of each phase (decode, h2d_ingest, encode, forward, d2h, write; device phases from events) and wall.
+    ``fusion`` (eval_io.run_test's resident path): ``(begin, end)``; ``begin(scene)`` -> a ``fusion.ScanFusion`` that gets
+    every depth / confidence map right after ``forward_features``, still on the device, with the camera as ``write_cam``
+    writes it and, as the image, the decoded bytes of the JPEG written; ``end(scene, fz)`` after the scene's last map.
+    ``stats`` then also gets fused_views, fusion_peak_bytes and the phases fuse (device) and fuse_write (host)."""
     device = torch.device(device)
     if device.type != "cuda":
         raise DmvsError("the scan-level path runs on a HIP device only")
     if device.index is None:   # "cuda": the current device, where the default path's .to(device) puts its tensors
         device = torch.device("cuda", torch.cuda.current_device())
+    if fusion is not None and not write_images:
+        raise DmvsError("resident fusion takes its colours from the reference images step 1 writes (write_images=True)")
     network.eval()
     num_stage = len(network.ndepths)
     t_start = time.perf_counter()
@@ -269,6 +276,8 @@ def save_depth_maps_cached(network, datapath: str, testlist: Sequence[str], outd
     written, n_maps, n_images = [], 0, 0
     errors: list = []
     write_q: "queue.Queue" = queue.Queue(maxsize=8)
+    pending: list = []              # image futures handed to fusion, failed on the way out if never filled
+    fused_views, fusion_peak = 0, 0
 
     def writer():
         while True:
@@ -276,10 +285,12 @@ def save_depth_maps_cached(network, datapath: str, testlist: Sequence[str], outd
             if job is None:
                 return
             if errors:
+                if job[-1] is not None:
+                    job[-1].set_exception(DmvsError("scan writer stopped after an earlier error"))
                 continue
             try:
                 t0 = time.perf_counter()
-                paths, ev, depth, conf, cam, img = job
+                paths, ev, depth, conf, cam, img, fut = job
                 ev.synchronize()
                 for p in paths.values():
                     os.makedirs(os.path.dirname(p), exist_ok=True)
@@ -289,10 +300,20 @@ def save_depth_maps_cached(network, datapath: str, testlist: Sequence[str], outd
                 if img is not None:
                     from PIL import Image
                     a = np.clip(np.transpose(img.numpy(), (1, 2, 0)) * 255, 0, 255).astype(np.uint8)
-                    Image.fromarray(a).save(paths["images"])
+                    if fut is None:
+                        Image.fromarray(a).save(paths["images"])
+                    else:   # the same encoder call into memory; fusion gets the pixels fuse_scene would decode
+                        buf = io.BytesIO()
+                        Image.fromarray(a).save(buf, format="JPEG")
+                        with open(paths["images"], "wb") as f:
+                            f.write(buf.getvalue())
+                        with Image.open(io.BytesIO(buf.getvalue())) as im:
+                            fut.set_result(np.asarray(im))
                 phases.add("write", time.perf_counter() - t0)
             except BaseException as e:   # re-raised on the main thread
                 errors.append(e)
+                if fut is not None and not fut.done():
+                    fut.set_exception(e)
 
     def timed_decode(path):
         t0 = time.perf_counter()
@@ -304,11 +325,13 @@ def save_depth_maps_cached(network, datapath: str, testlist: Sequence[str], outd
     wthread.start()
     pool = ThreadPoolExecutor(max_workers=max(1, int(workers)), thread_name_prefix="dmvs-scan-decode")
     cache = None
+    fz = None
     try:
         for scene in testlist:
             sc = (scene_cfg or {}).get(scene, {})
             plan = ScanPlan(datapath, scene, num_view, numdepth, interval_scale, inverse_depth,
                             sc.get("max_h", max_h), sc.get("max_w", max_w), fix_res)
+            fz = fusion[0](scene) if fusion is not None else None
             network.prepare(device)
             fp = hash(network._fingerprint(device))
             fdt = network.feature_dtype
@@ -408,7 +431,13 @@ def save_depth_maps_cached(network, datapath: str, testlist: Sequence[str], outd
                          (("depth_est", ".pfm"), ("confidence", ".pfm"), ("cams", "_cam.txt"), ("images", ".jpg"))}
                 if write_images and img is None:
                     raise DmvsError(f"reference image of {s.filename} was not kept")   # (every reference key is ingested first)
-                write_q.put((paths, ev, depth, conf, s.proj_matrices["stage{}".format(num_stage)][0], img))
+                cam = s.proj_matrices["stage{}".format(num_stage)][0]
+                fut = None
+                if fz is not None:
+                    fut = Future()
+                    pending.append(fut)
+                    fz.add(s.view_ids[0], out["depth"][0], out["photometric_confidence"][0], as_written_cam(cam), fut)
+                write_q.put((paths, ev, depth, conf, cam, img, fut))
                 written.append(paths["depth_est"])
                 n_maps += 1
                 if errors:
@@ -416,10 +445,24 @@ def save_depth_maps_cached(network, datapath: str, testlist: Sequence[str], outd
             cache.clear()
             if errors:
                 break
+            if fz is not None:
+                t0 = time.perf_counter()
+                fusion[1](scene, fz)
+                phases.add("fuse_write", time.perf_counter() - t0)
+                fused_views += fz.fused_views()
+                fusion_peak = max(fusion_peak, fz.peak_bytes)
+                if stats is not None:
+                    phases.add("fuse", fz.device_seconds())
+                fz = None
     finally:
         write_q.put(None)
         wthread.join()
         pool.shutdown(wait=True)
+        for fut in pending:
+            if not fut.done():
+                fut.set_exception(DmvsError("scan driver stopped before this image was written"))
+        if fz is not None:
+            fz.close()
     if errors:
         raise errors[0]
     if stats is not None:
@@ -427,7 +470,17 @@ def save_depth_maps_cached(network, datapath: str, testlist: Sequence[str], outd
         cs = dict(cache.stats) if cache is not None else dict(encodes=0, hits=0, misses=0, evictions=0, peak_bytes=0)
         stats.update(maps=n_maps, images=n_images, budget=cache.max_bytes if cache is not None else max_bytes, **cs,
                      phases_s=phases.result(), wall_s=time.perf_counter() - t_start)
+        if fusion is not None:
+            stats.update(fused_views=fused_views, fusion_peak_bytes=fusion_peak)
     return written
+
+
+def as_written_cam(cam: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(K [3,3], E [4,4]) of a [2,4,4] cam exactly as fusion.read_camera_parameters reads back what eval_io.write_cam writes
+    (``str()`` of each fp32 value, parsed as fp32: the same text, the same parse)."""
+    def parse(a):
+        return np.array(" ".join(str(v) for v in a.ravel()).split(), dtype=np.float32).reshape(a.shape)
+    return parse(cam[1][:3, :3]), parse(cam[0])
 
 
 def _to_pinned(t: torch.Tensor) -> torch.Tensor:

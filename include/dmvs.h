@@ -366,6 +366,32 @@ int dmvs_geo_consistency_ladder(const float* depth_ref, const float* depth_src, 
                                 float dist_base, float rel_base, int* level_votes, unsigned char* mask,
                                 float* depth_reproj, int* vote_sum, float* depth_sum, dmvs_stream_t stream);
 
+/* N4, scan-level fusion (fusion.ScanFusion): one launch per reference view against all of its sources.
+ *   DMVS_FUSE_MAX_SRC sources at most (10 for the dynamic variant: its geo mask reads the nine gates up to i = nsrc).
+ *   dmvs_fuse_workgroups(H, W): number of workgroups of both launches = the length of `counts` (offsets: + 1).
+ *   dmvs_fuse_view: depth_ref, conf3 / conf2 / conf1 [H][W] (pass conf3 for a missing stage map); depth_src: a HOST
+ *     array of nsrc device pointers; proj33: a HOST array of nsrc x 33 floats (fusion.fold_projection per pair, in pair
+ *     order).  Per pixel, with the per-pair arithmetic of dmvs_geo_consistency(_ladder) (gates dist / rel; the ladder's
+ *     bases when dynamic) accumulated in registers:
+ *       photo = conf3 > t3 && conf2 > t2 && conf1 > t1
+ *       geo   = votes >= thres_view (static) | votes >= nsrc + 1 || any_{i=2..nsrc} level[i-2] >= i (dynamic)
+ *       masks [3][H][W] u8: photo, geo, photo && geo as 0 / 255
+ *       depth_avg [H][W] = (float)avg, depth_avg64 [H][W] = avg at final pixels only, where
+ *       avg = (double)(sum + d_base) / (double)(votes + 1), d_base = 1e-4f for a zero depth (static), else the depth
+ *     counts [workgroups] i32: final pixels per workgroup.
+ *   dmvs_fuse_emit: offsets [workgroups + 1] i32 (exclusive scan of counts; offsets[workgroups] = total) and the world
+ *     points xyz [total][3] fp32 of the final pixels in row-major order: Einv . [Kinv . (x d, y d, d); 1] in fp64 with
+ *     kinv9 / einv16 HOST arrays (row-major), rounded to fp32.  xyz must hold H * W points (the total is not known on
+ *     the host when the launch is enqueued). */
+#define DMVS_FUSE_MAX_SRC 16
+long dmvs_fuse_workgroups(int H, int W);
+int dmvs_fuse_view(const float* depth_ref, const float* conf3, const float* conf2, const float* conf1, int H, int W,
+                   int nsrc, const float* const* depth_src, const float* proj33, float t1, float t2, float t3,
+                   int dynamic, int thres_view, float dist, float rel, unsigned char* masks, float* depth_avg,
+                   double* depth_avg64, int* counts, dmvs_stream_t stream);
+int dmvs_fuse_emit(const unsigned char* masks, const double* depth_avg64, const int* counts, int H, int W,
+                   const double* kinv9, const double* einv16, int* offsets, float* xyz, dmvs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,11 @@
-"""Development: VGPR / AGPR / LDS / spill counts of every kernel in a hipcc -S listing (stdin or file)."""
+"""Development: VGPR / AGPR / LDS / spill / scratch counts of every kernel in a hipcc -S listing or in the
+`llvm-readelf --notes` of a code object (stdin or file)."""
 import re
 import subprocess
 import sys
 
 text = open(sys.argv[1]).read() if len(sys.argv) > 1 else sys.stdin.read()
-keys = ("name", "vgpr_count", "agpr_count", "group_segment_fixed_size", "vgpr_spill_count")
+keys = ("name", "vgpr_count", "agpr_count", "group_segment_fixed_size", "vgpr_spill_count", "private_segment_fixed_size")
 cur = {}
 rows = []
 for line in text.splitlines():
@@ -18,4 +19,4 @@ names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), ca
 for r, n in zip(rows, names):
     n = n.replace("(anonymous namespace)::", "").replace("void ", "")
     n = re.sub(r"\(.*\)$", "", n)
-    print(f"{n:64s} vgpr {r['vgpr_count']:>4s} agpr {r['agpr_count']:>3s} lds {r['group_segment_fixed_size']:>6s} spill {r['vgpr_spill_count']}")
+    print(f"{n:64s} vgpr {r['vgpr_count']:>4s} agpr {r['agpr_count']:>3s} lds {r['group_segment_fixed_size']:>6s} spill {r['vgpr_spill_count']} scratch {r['private_segment_fixed_size']}")
