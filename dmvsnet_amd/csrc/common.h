@@ -27,6 +27,16 @@ typedef float float2_t __attribute__((ext_vector_type(2)));
 // is the largest one and a (x, z) slab of tiles fits the L2), else x, y, z (per-slice 2D kernels).
 static inline unsigned xcd_grid(int ntiles) { return 8u * (unsigned)((ntiles + 7) / 8); }
 
+// Host side of every Winograd F(2x2, 3x3) filter packer (K3w, K3r, K3z): (G g G^T)[i][p] of one 3x3 filter g[ky * 3 + kx],
+// formed in double in a fixed order (ky outer) and rounded once by the caller.
+static inline double wino_filter(const double g[9], int i, int p) {
+    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    double u = 0.0;
+    for (int ky = 0; ky < 3; ++ky)
+        for (int kx = 0; kx < 3; ++kx) u += Gm[i][ky] * Gm[p][kx] * g[ky * 3 + kx];
+    return u;
+}
+
 #ifdef __HIPCC__
 __device__ __forceinline__ bool xcd_tile(int nx, int ny, int nz, bool z_fast, int& bx, int& by, int& bz) {
     const int n = nx * ny * nz, per = (n + 7) >> 3;

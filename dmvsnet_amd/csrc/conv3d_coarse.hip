@@ -400,7 +400,6 @@ extern "C" long dmvs_conv3d_coarse_weight_floats(int Cin, int Cout, int kdepth) 
 extern "C" int dmvs_pack_conv_weights_coarse(const float* w, float* out, int Cin, int Cout, int kdepth) {
     const RCfg* c = find_rcfg(Cin, Cout, kdepth);
     if (!c || !w || !out) return DMVS_EUNSUPPORTED;
-    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
     const int NT = 9 * kdepth, cps = kdepth == 3 ? 16 : 32, nst = Cin / cps, gph = cps / 8, ncg = Cout / (16 * c->ncb);
     size_t n = 0;
     // order: cout group, wave (i = transform row, h = channel half of a stage), stage, k-group, kz, block, lane, position p
@@ -414,11 +413,9 @@ extern "C" int dmvs_pack_conv_weights_coarse(const float* w, float* out, int Cin
                                 for (int p = 0; p < 4; ++p) {
                                     const int i = wave & 3, h = wave >> 2;
                                     const int ci = s * cps + (h * gph + gg) * 4 + l / 16, co = (cg * c->ncb + nb) * 16 + l % 16;
-                                    double u = 0.0;   // (G g G^T)[i][p], formed in double and rounded once
-                                    for (int ky = 0; ky < 3; ++ky)
-                                        for (int kx = 0; kx < 3; ++kx)
-                                            u += Gm[i][ky] * Gm[p][kx] * (double)w[((size_t)co * Cin + ci) * NT + (kz * 3 + ky) * 3 + kx];
-                                    out[n++] = (float)u;
+                                    double g[9];
+                                    for (int t = 0; t < 9; ++t) g[t] = w[((size_t)co * Cin + ci) * NT + kz * 9 + t];
+                                    out[n++] = (float)wino_filter(g, i, p);
                                 }
     return n == (size_t)dmvs_conv3d_coarse_weight_floats(Cin, Cout, kdepth) ? 0 : DMVS_EINVAL;
 }

@@ -855,9 +855,9 @@ extern "C" long dmvs_conv3d_wino_weight_floats(int Cin, int Cout, int kdepth) {
 extern "C" int dmvs_pack_conv_weights_wino(const float* w, float* out, int Cin, int Cout, int kdepth) {
     const WCfg* c = find_wcfg(Cin, Cout, kdepth);
     if (!c || !w || !out) return DMVS_EUNSUPPORTED;
-    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
     const int NT = 9 * kdepth, cich = 4 * c->GPC;
     size_t n = 0;
+    double g[9];
     if (Cin == 2) {   // conv0_wino_kernel: k-step, quarter, lane (cout = l % 16, channel = (l / 16) & 1, depth selector l / 32), xi % 4
         for (int st = 0; st < 2; ++st)
             for (int q = 0; q < 4; ++q)
@@ -865,29 +865,23 @@ extern "C" int dmvs_pack_conv_weights_wino(const float* w, float* out, int Cin, 
                     for (int e = 0; e < 4; ++e) {
                         const int xi = 4 * q + e, ya = xi / 4, xb = xi % 4, co = l % 16, ci = (l / 16) & 1, zsel = l / 32;
                         const int kz = st ? 2 : zsel;
-                        double u = 0.0;
-                        for (int ky = 0; ky < 3; ++ky)
-                            for (int kx = 0; kx < 3; ++kx)
-                                u += Gm[ya][ky] * Gm[xb][kx] * (double)w[((size_t)co * Cin + ci) * NT + (kz * 3 + ky) * 3 + kx];
-                        out[n++] = (st == 1 && zsel == 1) ? 0.f : (float)u;
+                        for (int t = 0; t < 9; ++t) g[t] = w[((size_t)co * Cin + ci) * NT + kz * 9 + t];
+                        out[n++] = (st == 1 && zsel == 1) ? 0.f : (float)wino_filter(g, ya, xb);
                     }
         return n == 2048 ? 0 : DMVS_EINVAL;
     }
     // order: chunk, kz, k-group, 16-channel block, quarter q of the 16 transform positions, lane, xi % 4
     for (int ci0 = 0; ci0 < Cin; ci0 += cich)
         for (int kz = 0; kz < kdepth; ++kz)
-            for (int g = 0; g < c->GPC; ++g)
+            for (int kg = 0; kg < c->GPC; ++kg)
                 for (int mb = 0; mb < c->MB; ++mb)
                     for (int q = 0; q < 4; ++q)
                         for (int l = 0; l < 64; ++l)
                             for (int e = 0; e < 4; ++e) {
                                 const int xi = 4 * q + e, ya = xi / 4, xb = xi % 4;
-                                const int co = mb * 16 + l % 16, ci = ci0 + 4 * g + l / 16;
-                                double u = 0.0;   // (G g G^T)[ya][xb], formed in double and rounded once
-                                for (int ky = 0; ky < 3; ++ky)
-                                    for (int kx = 0; kx < 3; ++kx)
-                                        u += Gm[ya][ky] * Gm[xb][kx] * (double)w[((size_t)co * Cin + ci) * NT + (kz * 3 + ky) * 3 + kx];
-                                out[n++] = co < Cout ? (float)u : 0.f;
+                                const int co = mb * 16 + l % 16, ci = ci0 + 4 * kg + l / 16;
+                                for (int t = 0; t < 9; ++t) g[t] = w[((size_t)co * Cin + ci) * NT + kz * 9 + t];
+                                out[n++] = co < Cout ? (float)wino_filter(g, ya, xb) : 0.f;
                             }
     return n == (size_t)dmvs_conv3d_wino_weight_floats(Cin, Cout, kdepth) ? 0 : DMVS_EINVAL;
 }
@@ -922,13 +916,6 @@ extern "C" long dmvs_conv3d_wino_fpn_weight_floats(void) { return 3 * 4 * 256 + 
 extern "C" int dmvs_pack_conv_weights_wino_fpn(const float* w3, const float* w_lat, const float* b_lat, float* out) {
     if (!w3 || !w_lat || !b_lat || !out) return DMVS_EINVAL;
     constexpr int Cout = 16, Cin = 32, Cl = 8;
-    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    auto U = [&](const double g[9], int ya, int xb) {
-        double u = 0.0;
-        for (int ky = 0; ky < 3; ++ky)
-            for (int kx = 0; kx < 3; ++kx) u += Gm[ya][ky] * Gm[xb][kx] * g[ky * 3 + kx];
-        return u;
-    };
     size_t n = 0;
     // lateral part: composite filters W3 o W_lat (channels 0-7) and W3 . b_lat (the ones plane, k-slot 0 of group 2)
     for (int c = 0; c < 3; ++c)
@@ -947,7 +934,7 @@ extern "C" int dmvs_pack_conv_weights_wino_fpn(const float* w3, const float* w_l
                         g[t] = acc;
                     }
                     if (c == 2 && kslot > 0) zero = true;
-                    out[n++] = zero ? 0.f : (float)U(g, xi / 4, xi % 4);
+                    out[n++] = zero ? 0.f : (float)wino_filter(g, xi / 4, xi % 4);
                 }
     // top-down part: positions {0, 1, 3} x {0, 1, 3}; position 1 carries the factor 2 of B^T d = 2 T1
     static const int pos[3] = {0, 1, 3};
@@ -960,7 +947,7 @@ extern "C" int dmvs_pack_conv_weights_wino_fpn(const float* w3, const float* w_l
                     const int ya = pos[j / 3], xb = pos[j % 3];
                     double g[9];
                     for (int t = 0; t < 9; ++t) g[t] = w3[((size_t)co * Cin + ci) * 9 + t];
-                    out[n++] = (float)(U(g, ya, xb) * (ya == 1 ? 2.0 : 1.0) * (xb == 1 ? 2.0 : 1.0));
+                    out[n++] = (float)(wino_filter(g, ya, xb) * (ya == 1 ? 2.0 : 1.0) * (xb == 1 ? 2.0 : 1.0));
                 }
     (void)Cout;
     return n == (size_t)dmvs_conv3d_wino_fpn_weight_floats() ? 0 : DMVS_EINVAL;

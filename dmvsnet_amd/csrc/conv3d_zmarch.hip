@@ -37,20 +37,15 @@
 #include <algorithm>
 #include <type_traits>
 
-#ifndef DMVS_K3Z_RING
-#define DMVS_K3Z_RING 2   /* LDS plane slots (the barrier-in-the-middle pipeline needs exactly two) */
-#endif
 #ifndef DMVS_ZKO
 #define DMVS_ZKO 0   /* development knock-outs (scripts/dev/variant_build.sh): 1 no tile loads, 2 no output stores, 4 no MFMAs, 8 no barrier, 16 no finish (exchange reads + output transform rows) */
 #endif
 #include "dev_guard.h"   // after the defaults of this file's development switches
 
-// persistent workgroups of a K3z launch (dmvs_tune("k3z_grid"), a multiple of 8); 0 = as many as are resident (3 or 2 per CU)
+// persistent workgroups of a K3z launch (dmvs_tune("k3z_grid"), a multiple of 8); 0 = as many as are resident (2 per CU)
 long g_k3z_grid = 0;
 // cap of a z segment's length (dmvs_tune("k3z_zs")); 0 = none: a segment is a whole column, or what a workgroup's plane range cuts out of one
 long g_k3z_zs = 0;
-// ring of 3 only: 1 = counted vmcnt at the stage wait, 0 = vmcnt(0) (dmvs_tune("k3z_counted_wait"), bit-identical: the gate)
-long g_k3z_counted_wait = 1;
 
 namespace {
 
@@ -70,7 +65,6 @@ struct ZArgs {
     const float* shift;
     int D, H, W, relu;
     int ngx, ngy, zs;         // 8 x 8-output groups along x / y; cap of a z segment's length (>= D: none)
-    int counted;
 };
 
 template <int RING>
@@ -449,7 +443,6 @@ extern "C" long dmvs_conv3d_zmarch_weight_floats(int Cin, int Cout, int kdepth) 
 
 extern "C" int dmvs_pack_conv_weights_zmarch(const float* w, float* out, int Cin, int Cout, int kdepth) {
     if (!w || !out || !zmarch_shape(Cin, Cout, kdepth)) return DMVS_EUNSUPPORTED;
-    static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
     size_t n = 0;
     // order: wave (= transform row i), k-group, kz, lane (cout = l % 16, channel = 4 kg + l / 16), position p
     for (int i = 0; i < 4; ++i)
@@ -458,11 +451,9 @@ extern "C" int dmvs_pack_conv_weights_zmarch(const float* w, float* out, int Cin
                 for (int l = 0; l < 64; ++l)
                     for (int p = 0; p < 4; ++p) {
                         const int ci = 4 * kg + l / 16, co = l % 16;
-                        double u = 0.0;   // (G g G^T)[i][p], formed in double and rounded once
-                        for (int ky = 0; ky < 3; ++ky)
-                            for (int kx = 0; kx < 3; ++kx)
-                                u += Gm[i][ky] * Gm[p][kx] * (double)w[((size_t)co * Cin + ci) * 27 + (kz * 3 + ky) * 3 + kx];
-                        out[n++] = (float)u;
+                        double g[9];
+                        for (int t = 0; t < 9; ++t) g[t] = w[((size_t)co * Cin + ci) * 27 + kz * 9 + t];
+                        out[n++] = (float)wino_filter(g, i, p);
                     }
     return n == (size_t)dmvs_conv3d_zmarch_weight_floats(Cin, Cout, kdepth) ? 0 : DMVS_EINVAL;
 }
@@ -479,6 +470,5 @@ extern "C" int dmvs_conv3d_zmarch(const float* in, float* out, const float* w_pa
     a.in = in; a.out = out; a.w = w_packed; a.scale = scale; a.shift = shift;
     a.D = D; a.H = H; a.W = W; a.relu = (flags & DMVS_RELU) ? 1 : 0;
     a.ngx = ceil_div(W, 8); a.ngy = ceil_div(H, 8);
-    a.counted = g_k3z_counted_wait ? 1 : 0;
-    return launch_zmarch<DMVS_K3Z_RING>(a, (hipStream_t)stream);
+    return launch_zmarch<2>(a, (hipStream_t)stream);   // RING = 2 LDS plane slots: the barrier-in-the-middle pipeline needs exactly two
 }

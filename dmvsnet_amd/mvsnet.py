@@ -73,17 +73,10 @@ class FeatureNet(nn.Module):
     def pack(self):
         """Fold BatchNorm and pack every layer for the MFMA conv kernel (kdepth = 1: views are depth slices)."""
         def layer(name, w, mode, scale, shift, relu):
-            cout, cin = w.shape[0], w.shape[1]
-            wm = ops.pack_mfma(w, cin, cout, mode, 1)
-            if wm is None:
-                raise DmvsError(f"FeatureNet layer {name} ({cin}->{cout}) is not covered by the MFMA kernel")
-            ww = ops.pack_wino(w, cin, cout, 1) if (mode == ops.CONV_S1 and w.shape[-1] == 3) else None
-            # conv2.1 / conv2.2 are the 32 -> 32 2D shape K3r compiles (ops.use_coarse_feature)
-            wr = ops.pack_coarse(w, cin, cout, 1) if (ops.use_coarse_feature and mode == ops.CONV_S1 and w.shape[-1] == 3) else None
-            return ops.ConvLayer("feature." + name, mode, 1, cin, cout, None, wm.to(w.device),
-                                 None if scale is None else scale.detach().contiguous(),
-                                 None if shift is None else shift.detach().contiguous(), relu,
-                                 None if ww is None else ww.to(w.device), w_coarse=None if wr is None else wr.to(w.device))
+            L = ops.make_layer("feature." + name, mode, w, scale, shift, relu, direct=False, coarse=ops.use_coarse_feature)
+            if L.w_mfma is None:
+                raise DmvsError(f"FeatureNet layer {name} ({L.cin}->{L.cout}) is not covered by the MFMA kernel")
+            return L
 
         L = {}
         spec = (("conv0.0", self.conv0[0], ops.CONV_S1), ("conv0.1", self.conv0[1], ops.CONV_S1),
@@ -91,24 +84,16 @@ class FeatureNet(nn.Module):
                 ("conv1.2", self.conv1[2], ops.CONV_S1), ("conv2.0", self.conv2[0], ops.CONV2D_K5S2),
                 ("conv2.1", self.conv2[1], ops.CONV_S1), ("conv2.2", self.conv2[2], ops.CONV_S1))
         for name, m, mode in spec:
-            w = m.conv.weight.detach()
-            if w.shape[1] == 3:  # RGB + one zero channel: the MFMA k-group is 4 channels wide
-                w = torch.cat((w, torch.zeros_like(w[:, :1])), 1).contiguous()
             scale, shift = m.folded()
-            L[name] = layer(name, w, mode, scale, shift, True)
-            if name.startswith("conv0."):   # the two 8-channel full-resolution layers: K3s (row sweep on the 4x4x1 MFMA)
-                wc = ops.pack_c8(m.conv.weight.detach())
-                L[name].w_c8 = None if wc is None else wc.to(w.device)
+            L[name] = layer(name, m.conv.weight, mode, scale, shift, True)
         one = lambda n: torch.ones(n, device=self.out1.weight.device)
-        L["out1"] = layer("out1", self.out1.weight.detach(), ops.CONV2D_K1, None, None, False)
-        L["inner1"] = layer("inner1", self.inner1.weight.detach(), ops.CONV2D_K1, one(self.inner1.out_channels),
-                            self.inner1.bias, False)
-        L["inner2"] = layer("inner2", self.inner2.weight.detach(), ops.CONV2D_K1, one(self.inner2.out_channels),
-                            self.inner2.bias, False)
+        L["out1"] = layer("out1", self.out1.weight, ops.CONV2D_K1, None, None, False)
+        L["inner1"] = layer("inner1", self.inner1.weight, ops.CONV2D_K1, one(self.inner1.out_channels), self.inner1.bias, False)
+        L["inner2"] = layer("inner2", self.inner2.weight, ops.CONV2D_K1, one(self.inner2.out_channels), self.inner2.bias, False)
         self._inner2_w = self.inner2.weight.detach().reshape(self.inner2.out_channels, -1).contiguous()   # [32, 8]
         self._inner2_b = self.inner2.bias.detach().contiguous()
-        L["out2"] = layer("out2", self.out2.weight.detach(), ops.CONV_S1, None, None, False)
-        L["out3"] = layer("out3", self.out3.weight.detach(), ops.CONV_S1, None, None, False)
+        L["out2"] = layer("out2", self.out2.weight, ops.CONV_S1, None, None, False)
+        L["out3"] = layer("out3", self.out3.weight, ops.CONV_S1, None, None, False)
         wf = ops.pack_wino_fpn(self.out3.weight.detach(), self._inner2_w, self._inner2_b)   # inner2 folded into out3
         L["out3"].w_wino_fpn = None if wf is None else wf.to(self.out3.weight.device)
         self._packed = L
@@ -192,37 +177,15 @@ class _RegBranch(nn.Module):
         for name, mode in self._SPEC:
             m: _ConvBn = getattr(self, name)
             w = m.conv.weight.detach()
-            kd = 1 if w.dim() == 4 else 3
-            tr = mode == ops.DECONV_S2
-            cin, cout = (w.shape[0], w.shape[1]) if tr else (w.shape[1], w.shape[0])
             scale, shift = m.folded()
-            wm = ops.pack_mfma(w, cin, cout, mode, kd)
-            ww = ops.pack_wino(w, cin, cout, kd) if mode == ops.CONV_S1 else None
-            wr = ops.pack_coarse(w, cin, cout, kd) if mode == ops.CONV_S1 else None
-            wz = ops.pack_zmarch(w, cin, cout, kd) if mode == ops.CONV_S1 else None
-            layers[name] = ops.ConvLayer(f"{tag}.{name}", mode, kd, cin, cout, ops.pack_direct(w, tr),
-                                         None if wm is None else wm.to(w.device), scale.detach().contiguous(),
-                                         shift.detach().contiguous(), True, None if ww is None else ww.to(w.device),
-                                         w_coarse=None if wr is None else wr.to(w.device),
-                                         w_zmarch=None if wz is None else wz.to(w.device))
-            if name == "conv1":   # the bf16-split PROBE's operands (ops.split_probe; off in the product)
-                ws = ops.pack_split(w)
-                layers[name].w_split = None if ws is None else ws.to(w.device)
-            if kd == 3 and mode == ops.CONV_S1:
+            layers[name] = ops.make_layer(f"{tag}.{name}", mode, w, scale, shift, True)
+            if w.dim() == 5 and mode == ops.CONV_S1:
                 # On a volume of depth 1 the outer depth taps only ever meet zero padding: the middle 3x3 slice as a
                 # per-slice 2D conv gives the same sums with a third of the MFMA work (refine conv4, stage-3 conv6)
-                w2 = w[:, :, 1].contiguous()
-                wm2 = ops.pack_mfma(w2, cin, cout, mode, 1)
-                if wm2 is not None:
-                    ww2 = ops.pack_wino(w2, cin, cout, 1)
-                    wr2 = ops.pack_coarse(w2, cin, cout, 1)
-                    layers[name + "@d1"] = ops.ConvLayer(f"{tag}.{name}@d1", mode, 1, cin, cout, None, wm2.to(w.device),
-                                                         scale.detach().contiguous(), shift.detach().contiguous(), True,
-                                                         None if ww2 is None else ww2.to(w.device),
-                                                         w_coarse=None if wr2 is None else wr2.to(w.device))
-        w = self.prob.weight.detach()
-        layers["prob"] = ops.ConvLayer(f"{tag}.prob", ops.CONV_S1, 3, w.shape[1], 2, ops.pack_direct(w, False), None,
-                                       None, None, False)
+                d1 = ops.make_layer(f"{tag}.{name}@d1", mode, w[:, :, 1].contiguous(), scale, shift, True, direct=False)
+                if d1.w_mfma is not None:
+                    layers[name + "@d1"] = d1
+        layers["prob"] = ops.make_layer(f"{tag}.prob", ops.CONV_S1, self.prob.weight, None, None, False)
         return layers
 
 
@@ -250,11 +213,7 @@ class CostRegNet(nn.Module):
         w = torch.cat((s.conv0.conv.weight.detach(), h.conv0.conv.weight.detach()), 0)
         sc_s, sh_s = s.conv0.folded()
         sc_h, sh_h = h.conv0.folded()
-        wm = ops.pack_mfma(w, w.shape[1], w.shape[0], ops.CONV_S1, 3)
-        ww = ops.pack_wino(w, w.shape[1], w.shape[0], 3)
-        conv0 = ops.ConvLayer(f"{tag}.conv0x2", ops.CONV_S1, 3, w.shape[1], w.shape[0], ops.pack_direct(w, False),
-                              None if wm is None else wm.to(w.device), torch.cat((sc_s, sc_h)).detach().contiguous(),
-                              torch.cat((sh_s, sh_h)).detach().contiguous(), True, None if ww is None else ww.to(w.device))
+        conv0 = ops.make_layer(f"{tag}.conv0x2", ops.CONV_S1, w, torch.cat((sc_s, sc_h)), torch.cat((sh_s, sh_h)), True)
         self._packed = (conv0, s.pack(tag + ".small"), h.pack(tag + ".huge"))
 
     def run(self, sim: torch.Tensor, backend: str, side: Optional[torch.cuda.Stream] = None, regress=None) -> torch.Tensor:
@@ -266,38 +225,25 @@ class CostRegNet(nn.Module):
         conv0, small, huge = self._packed
         b = conv0.cout // 2
         c0 = ops.conv3d(sim, conv0, backend=backend)
-        if regress is not None:
-            dsp = torch.empty((4,) + tuple(sim.shape[2:]), dtype=torch.float32, device=sim.device)
-            main = torch.cuda.current_stream()
-            if side is not None:
-                side.wait_stream(main)
-            ok = True
-            for i, L in enumerate((small, huge)):
-                ctx = torch.cuda.stream(side) if (side is not None and i == 1) else _NullCtx()
-                with ctx:
-                    ok = self._branch(c0[i * b:(i + 1) * b], L, dsp[2 * i:2 * i + 2], backend, regress) and ok
-            if side is not None:
-                main.wait_stream(side)
-                for t in (c0, dsp):
-                    t.record_stream(side)
-            if ok:
-                return dsp
-            return self.run(sim, backend, side)     # (never at the product's shapes: W % 4 and alignment are checked up front)
-        logits = torch.empty((4,) + tuple(sim.shape[1:]), dtype=torch.float32, device=sim.device)
+        out = torch.empty((4,) + tuple(sim.shape[1 if regress is None else 2:]), dtype=torch.float32, device=sim.device)
         # The two U-Nets are independent (module.py:347-348): the `huge` branch runs on a second HIP stream so
         # its kernels fill the load / epilogue stalls of the `small` branch's kernels (and vice versa).
         main = torch.cuda.current_stream()
         if side is not None:
             side.wait_stream(main)
+        ok = True
         for i, L in enumerate((small, huge)):
-            ctx = torch.cuda.stream(side) if (side is not None and i == 1) else _NullCtx()
-            with ctx:
-                self._branch(c0[i * b:(i + 1) * b], L, logits[2 * i:2 * i + 2], backend)
+            with torch.cuda.stream(side) if (side is not None and i == 1) else _NullCtx():
+                ok = self._branch(c0[i * b:(i + 1) * b], L, out[2 * i:2 * i + 2], backend, regress) and ok
         if side is not None:
             main.wait_stream(side)
-            for t in (c0, logits):
+            for t in (c0, out):
                 t.record_stream(side)
-        return logits
+        if ok:
+            return out
+        # a `prob` head declined by dmvs_prob_regress (ops.prob_fusable checks D and W % 4, not the tensors' alignment): the
+        # whole call again, on logits
+        return self.run(sim, backend, side)
 
     @staticmethod
     def _branch(x0, L, out, backend, regress=None):
@@ -317,7 +263,8 @@ class CostRegNet(nn.Module):
         y = ops.conv3d(y, L["conv11"], skip=x0, backend=backend)
         if regress is not None:
             return ops.prob_regress(y, L["prob"], regress[0], regress[1], regress[2], out)
-        ops.conv3d(y, L["prob"], out=out, backend=backend)
+        # K2 is the only kernel for Cout = 2 (what `auto` picks too): "mfma" has no K3 form of this layer
+        ops.conv3d(y, L["prob"], out=out, backend="direct")
         return True
 
 
@@ -696,7 +643,7 @@ class MVSNet(nn.Module):
         key = (self._packed_key, tuple(imgs.shape), tuple(depth_values.shape),
                tuple((k, tuple(v.shape)) for k, v in sorted(proj_matrices.items())), self.return_prob_volume,
                self.return_depth_values, self.affine_hypotheses,
-               self.two_streams, self.conv_backend, self.feature_async_topdown, self.feature_group_views)
+               self.two_streams, self.conv_backend, self.feature_async_topdown, self.feature_group_views, ops.dispatch_key())
         if self._graph is None or self._graph[0] != key:
             self._graph = None
             s_imgs, s_dv = imgs.clone(), depth_values.clone()

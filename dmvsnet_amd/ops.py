@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence
 
 import torch
 
@@ -38,6 +38,10 @@ class KernelTimer:
         e = self._event()
         e.record()
         return e
+
+    def cancel(self, start):
+        """Give back the start event of a launch the kernel declined (it never ran)."""
+        self._pool.append(start)
 
     def end(self, family, start, flops, nbytes, exec_flops=None, label=None):
         """``flops`` = algorithmic (direct-form) FLOPs of the launch; ``exec_flops`` = what its MFMAs actually execute when
@@ -139,6 +143,29 @@ def _req(*ts: torch.Tensor) -> None:
             raise RuntimeError(f"expected float32 tensor, got {t.dtype}")  # same class the reference raises
         if not t.is_contiguous():
             raise _lib.DmvsError("non-contiguous tensor passed to a dmvs kernel")
+
+
+def _launch(fn, args, name: str, kernel: str, x: torch.Tensor, weights, decline: bool, family: str, cost, label=None) -> bool:
+    """Launch ``fn(*args, stream)``, logged and timed.  ``weights``: tensors the kernel reads by raw pointer besides the activations
+    ``x`` (one left on the CPU / another GPU would fault): they must be on x's device.  ``cost`` = (flops, bytes, executed flops) of
+    the timer record, None while no timer is set.  With ``decline``, DMVS_EUNSUPPORTED (the kernel does not cover the call) returns
+    False: nothing ran, nothing is logged or timed.  Every other failure raises."""
+    dev = x.get_device()   # (cheaper than comparing torch.device objects: this runs for every conv launch)
+    for t in weights:
+        if t is not None and t.get_device() != dev:
+            raise _lib.DmvsError(f"layer {name}: weights on {t.device}, activations on {x.device}")
+    t0 = timer.begin() if timer is not None else None
+    code = fn(*args, _stream())
+    if code:
+        if t0 is not None:
+            timer.cancel(t0)
+        if decline and code == _lib.EUNSUPPORTED:
+            return False
+        _lib.check(code, f"{kernel}[{name}]")
+    _log(family)
+    if t0 is not None:
+        timer.end(family, t0, *cost, label=label or name)
+    return True
 
 
 # ------------------------------------------------------------------------------------------ layout
@@ -381,58 +408,39 @@ def pack_direct(w: torch.Tensor, transposed: bool) -> torch.Tensor:
     return w.permute(2, 3, 4, 1, 0).contiguous()
 
 
-def pack_mfma(w: torch.Tensor, cin: int, cout: int, mode: int, kdepth: int) -> Optional[torch.Tensor]:
-    """Host-side packing into K3's fragment order via the library; None if K3 does not cover the shape."""
+def _pack(floats: str, pack: str, ws: Sequence[torch.Tensor], *shape: int) -> Optional[torch.Tensor]:
+    """Host-side packing through the library: ``floats(*shape)`` is the packed length (<= 0: the kernel does not compile the
+    shape -> None), ``pack(*ws, out, *shape)`` writes it."""
     lib = _lib.load()
-    n = lib.dmvs_conv3d_mfma_weight_floats(cin, cout, mode, kdepth)
+    n = getattr(lib, floats)(*shape)
     if n <= 0:
         return None
-    wc = w.detach().to("cpu", torch.float32).contiguous()
+    wc = [w.detach().to("cpu", torch.float32).contiguous() for w in ws]
     out = torch.empty(n, dtype=torch.float32)
-    _lib.check(lib.dmvs_pack_conv_weights_mfma(ctypes.c_void_p(wc.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                               cin, cout, mode, kdepth), "dmvs_pack_conv_weights_mfma")
+    _lib.check(getattr(lib, pack)(*(ctypes.c_void_p(w.data_ptr()) for w in wc), ctypes.c_void_p(out.data_ptr()), *shape), pack)
     return out
+
+
+def pack_mfma(w: torch.Tensor, cin: int, cout: int, mode: int, kdepth: int) -> Optional[torch.Tensor]:
+    """Host-side packing into K3's fragment order via the library; None if K3 does not cover the shape."""
+    return _pack("dmvs_conv3d_mfma_weight_floats", "dmvs_pack_conv_weights_mfma", (w,), cin, cout, mode, kdepth)
 
 
 def pack_wino(w: torch.Tensor, cin: int, cout: int, kdepth: int) -> Optional[torch.Tensor]:
     """Host-side G g G^T transform + packing for K3w (csrc/conv3d_wino.hip); None if the layer shape is not compiled."""
-    lib = _lib.load()
-    n = lib.dmvs_conv3d_wino_weight_floats(cin, cout, kdepth)
-    if n <= 0:
-        return None
-    wc = w.detach().to("cpu", torch.float32).contiguous()
-    out = torch.empty(n, dtype=torch.float32)
-    _lib.check(lib.dmvs_pack_conv_weights_wino(ctypes.c_void_p(wc.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                               cin, cout, kdepth), "dmvs_pack_conv_weights_wino")
-    return out
+    return _pack("dmvs_conv3d_wino_weight_floats", "dmvs_pack_conv_weights_wino", (w,), cin, cout, kdepth)
 
 
 def pack_coarse(w: torch.Tensor, cin: int, cout: int, kdepth: int) -> Optional[torch.Tensor]:
     """Host-side G g G^T transform + packing for K3r (csrc/conv3d_coarse.hip: the coarse-level conv4 / conv6 with the
     filters held in registers); None if the layer shape is not compiled."""
-    lib = _lib.load()
-    n = lib.dmvs_conv3d_coarse_weight_floats(cin, cout, kdepth)
-    if n <= 0:
-        return None
-    wc = w.detach().to("cpu", torch.float32).contiguous()
-    out = torch.empty(n, dtype=torch.float32)
-    _lib.check(lib.dmvs_pack_conv_weights_coarse(ctypes.c_void_p(wc.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                                 cin, cout, kdepth), "dmvs_pack_conv_weights_coarse")
-    return out
+    return _pack("dmvs_conv3d_coarse_weight_floats", "dmvs_pack_conv_weights_coarse", (w,), cin, cout, kdepth)
 
 
 def pack_zmarch(w: torch.Tensor, cin: int, cout: int, kdepth: int) -> Optional[torch.Tensor]:
     """Host-side G g G^T transform + packing for K3z (csrc/conv3d_zmarch.hip: conv2 marching along z with the filters held in
     registers); None if the layer shape is not compiled."""
-    lib = _lib.load()
-    n = lib.dmvs_conv3d_zmarch_weight_floats(cin, cout, kdepth)
-    if n <= 0:
-        return None
-    wc = w.detach().to("cpu", torch.float32).contiguous()
-    out = torch.empty(n, dtype=torch.float32)
-    _lib.check(lib.dmvs_pack_conv_weights_zmarch(ctypes.c_void_p(wc.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                                 cin, cout, kdepth), "dmvs_pack_conv_weights_zmarch")
-    return out
+    return _pack("dmvs_conv3d_zmarch_weight_floats", "dmvs_pack_conv_weights_zmarch", (w,), cin, cout, kdepth)
 
 
 def pack_split(w: torch.Tensor) -> Optional[torch.Tensor]:
@@ -440,12 +448,45 @@ def pack_split(w: torch.Tensor) -> Optional[torch.Tensor]:
     (csrc/conv3d_split.hip; never part of the product's dispatch); None for any other shape."""
     if tuple(w.shape) != (16, 8, 3, 3, 3):
         return None
-    lib = _lib.load()
-    wc = w.detach().to("cpu", torch.float32).contiguous()
-    out = torch.empty(lib.dmvs_conv3d_split_weight_floats(8, 16), dtype=torch.float32)
-    _lib.check(lib.dmvs_pack_conv_weights_split(ctypes.c_void_p(wc.data_ptr()), ctypes.c_void_p(out.data_ptr()), 8, 16),
-               "dmvs_pack_conv_weights_split")
-    return out
+    return _pack("dmvs_conv3d_split_weight_floats", "dmvs_pack_conv_weights_split", (w,), 8, 16)
+
+
+def pack_c8(w: torch.Tensor) -> Optional[torch.Tensor]:
+    """nn.Conv2d weight [8, Cin, 3, 3] -> K3s operand order (csrc/conv2d_c8.hip); None for any other shape."""
+    if w.dim() != 4 or w.shape[0] != 8 or tuple(w.shape[2:]) != (3, 3):
+        return None
+    return _pack("dmvs_conv2d_c8_weight_floats", "dmvs_pack_conv_weights_c8", (w,), int(w.shape[1]))
+
+
+def pack_wino_fpn(w3: torch.Tensor, w_lat: torch.Tensor, b_lat: torch.Tensor) -> Optional[torch.Tensor]:
+    """Composite Winograd filters of FeatureNet's level-3 merge (inner2 folded into out3, module.py:333-336) for
+    dmvs_conv3d_wino_fpn2; w3 [16,32,3,3], w_lat [32,8], b_lat [32].  None for any other shape."""
+    if tuple(w3.shape) != (16, 32, 3, 3) or tuple(w_lat.shape) != (32, 8) or tuple(b_lat.shape) != (32,):
+        return None
+    return _pack("dmvs_conv3d_wino_fpn_weight_floats", "dmvs_pack_conv_weights_wino_fpn", (w3, w_lat, b_lat))
+
+
+def make_layer(name: str, mode: int, w: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], relu: bool,
+               direct: bool = True, coarse: bool = True) -> ConvLayer:
+    """PyTorch conv weight (``mode`` DECONV_S2: transposed, [Cin][Cout][k..]; 4-D: a 2D layer, kdepth 1) + folded BatchNorm ->
+    ConvLayer with every kernel form that compiles the shape, each moved to the weight's device.  The Winograd family (K3w,
+    K3r, K3z) and K3s are packed for stride-1 3x3 layers only, the split probe for stride-2 ones; ``direct``: also the K2 form;
+    ``coarse``: also K3r.  A 3-channel (RGB) weight gets a zero fourth channel for K3 (4-channel k-groups); K3s reads the three."""
+    w = w.detach()
+    kd = 3 if w.dim() == 5 else 1
+    tr = mode == DECONV_S2
+    cin, cout = (w.shape[0], w.shape[1]) if tr else (w.shape[1], w.shape[0])
+    wk = w
+    if cin == 3:
+        wk, cin = torch.cat((w, torch.zeros_like(w[:, :1])), 1).contiguous(), 4
+    s3 = mode == CONV_S1 and w.shape[-1] == 3
+    dev = lambda t: None if t is None else t.to(w.device)
+    return ConvLayer(name, mode, kd, cin, cout, pack_direct(w, tr) if direct else None, dev(pack_mfma(wk, cin, cout, mode, kd)),
+                     None if scale is None else scale.detach().contiguous(), None if shift is None else shift.detach().contiguous(),
+                     relu, w_wino=dev(pack_wino(wk, cin, cout, kd)) if s3 else None,
+                     w_c8=dev(pack_c8(w)) if s3 else None, w_coarse=dev(pack_coarse(wk, cin, cout, kd)) if s3 and coarse else None,
+                     w_split=dev(pack_split(w)) if mode == CONV_S2 else None,
+                     w_zmarch=dev(pack_zmarch(wk, cin, cout, kd)) if s3 else None)
 
 
 # PROBE switch (VERDICT r05 item 3), never on in the product: 3 or 6 = run every conv1 (8 -> 16, stride 2) of the regularisation nets
@@ -462,28 +503,11 @@ def conv3d_split(x: torch.Tensor, layer: "ConvLayer", terms: int, out: Optional[
     Do, Ho, Wo = layer.out_shape(D, H, W)
     if out is None:
         out = torch.empty((16, Do, Ho, Wo), dtype=torch.float32, device=x.device)
-    t0 = timer.begin() if timer is not None else None
-    _lib.check(_lib.load().dmvs_conv3d_split_probe(_ptr(x), _ptr(out), _ptr(layer.w_split), _ptr(layer.scale), _ptr(layer.shift),
-                                                   D, H, W, int(terms), RELU if layer.relu else 0, _stream()), "dmvs_conv3d_split_probe")
-    _log("conv3d_mfma")
-    if t0 is not None:
-        fl = 2.0 * 27 * 8 * 16 * Do * Ho * Wo
-        timer.end("conv3d_mfma", t0, fl, 4.0 * (8 * D * H * W + 16 * Do * Ho * Wo), fl, label=layer.name)
-    return out
-
-
-def pack_c8(w: torch.Tensor) -> Optional[torch.Tensor]:
-    """nn.Conv2d weight [8, Cin, 3, 3] -> K3s operand order (csrc/conv2d_c8.hip); None for any other shape."""
-    if w.dim() != 4 or w.shape[0] != 8 or tuple(w.shape[2:]) != (3, 3):
-        return None
-    lib = _lib.load()
-    n = lib.dmvs_conv2d_c8_weight_floats(int(w.shape[1]))
-    if n <= 0:
-        return None
-    wc = w.detach().to("cpu", torch.float32).contiguous()
-    out = torch.empty(n, dtype=torch.float32)
-    _lib.check(lib.dmvs_pack_conv_weights_c8(ctypes.c_void_p(wc.data_ptr()), ctypes.c_void_p(out.data_ptr()), int(w.shape[1])),
-               "dmvs_pack_conv_weights_c8")
+    fl = 2.0 * 27 * 8 * 16 * Do * Ho * Wo
+    _launch(_lib.load().dmvs_conv3d_split_probe, (_ptr(x), _ptr(out), _ptr(layer.w_split), _ptr(layer.scale), _ptr(layer.shift),
+                                                   D, H, W, int(terms), RELU if layer.relu else 0),
+            layer.name, "conv3d_split", x, (layer.w_split, layer.scale, layer.shift), False, "conv3d_mfma",
+            (fl, 4.0 * (8 * D * H * W + 16 * Do * Ho * Wo), fl))
     return out
 
 
@@ -501,36 +525,13 @@ def featurenet_conv0(imgs: torch.Tensor, l0: "ConvLayer", l1: "ConvLayer", famil
     ts = (l0.w_c8, l0.scale, l0.shift, l1.w_c8, l1.scale, l1.shift)
     if any(t is None for t in ts):
         return None
-    for t in ts:
-        if t.device != imgs.device:
-            raise _lib.DmvsError(f"layer {l0.name}: weights on {t.device}, images on {imgs.device}")
     V, c3, H, W = imgs.shape
     assert c3 == 3, imgs.shape
     out = torch.empty((8, V, H, W), dtype=torch.float32, device=imgs.device)
-    t0 = timer.begin() if timer is not None else None
-    code = _lib.load().dmvs_featurenet_conv0(_ptr(imgs), _ptr(out), *(_ptr(t) for t in ts), V, H, W, _stream())
-    if code == _lib.EUNSUPPORTED:
-        if t0 is not None:
-            timer._pool.append(t0)
+    cost = (2.0 * 9 * (3 + 8) * 8 * V * H * W, 4.0 * (3 + 8) * V * H * W, 2.0 * 9 * (3 + 8) * 8 * V * H * W)
+    if not _launch(_lib.load().dmvs_featurenet_conv0, (_ptr(imgs), _ptr(out), *(_ptr(t) for t in ts), V, H, W), l0.name,
+                   "featurenet_conv0", imgs, ts, True, family or "conv3d_mfma", cost, label="feature.conv0.fused"):
         return None
-    _lib.check(code, "featurenet_conv0")
-    fam = family or "conv3d_mfma"
-    _log(fam)
-    if t0 is not None:
-        timer.end(fam, t0, 2.0 * 9 * (3 + 8) * 8 * V * H * W, 4.0 * (3 + 8) * V * H * W, label="feature.conv0.fused")
-    return out
-
-
-def pack_wino_fpn(w3: torch.Tensor, w_lat: torch.Tensor, b_lat: torch.Tensor) -> Optional[torch.Tensor]:
-    """Composite Winograd filters of FeatureNet's level-3 merge (inner2 folded into out3, module.py:333-336) for
-    dmvs_conv3d_wino_fpn2; w3 [16,32,3,3], w_lat [32,8], b_lat [32].  None for any other shape."""
-    if tuple(w3.shape) != (16, 32, 3, 3) or tuple(w_lat.shape) != (32, 8) or tuple(b_lat.shape) != (32,):
-        return None
-    lib = _lib.load()
-    c = [t.detach().to("cpu", torch.float32).contiguous() for t in (w3, w_lat, b_lat)]
-    out = torch.empty(lib.dmvs_conv3d_wino_fpn_weight_floats(), dtype=torch.float32)
-    _lib.check(lib.dmvs_pack_conv_weights_wino_fpn(*(ctypes.c_void_p(t.data_ptr()) for t in c), ctypes.c_void_p(out.data_ptr())),
-               "dmvs_pack_conv_weights_wino_fpn")
     return out
 
 
@@ -553,7 +554,7 @@ def _ones_hw(layer: "ConvLayer", H: int, W: int, device) -> torch.Tensor:
 # leaves them to the direct-form K3 kernel (A/B, parity tests)
 use_c8 = True
 # K3w (Winograd form of the stride-1 3x3 layers) is used wherever a layer carries w_wino and the call has no residual /
-# quad-planar output; False forces the direct-form K3 kernel everywhere (A/B, parity tests).
+# image-stack input; False forces the direct-form K3 kernel everywhere (A/B, parity tests).
 use_wino = True
 # ... for `auto` only on volumes of at least this many workgroups.  0 = always: the 1/8-scale layers of a few dozen workgroups
 # are 10-20 % slower in K3w than in the direct form (together ~0.02 ms per depth map), but a kernel choice that depends on
@@ -576,12 +577,47 @@ ZMARCH_MIN_DEPTH = 8
 use_coarse_feature = False
 
 
+@dataclass(frozen=True)
+class _Form:
+    """A specialised kernel form of a conv layer.  ``auto`` tries them in the order of _FORMS, before K3 / K2."""
+    backend: str      # its forced-backend name
+    weight: str       # ConvLayer attribute of its packed weights (None: the layer has no such form)
+    skip: bool        # covers a residual
+    q4: bool          # covers the quad-planar output
+    views: bool       # covers the image-stack input (DMVS_IN_VIEWS)
+    auto: Callable    # (layer, D, H, W) -> `auto` takes the form: module switches, depth / plan rule
+    entry: str        # C entry: (in, out, w, scale, shift, Cin, Cout, D, H, W, kdepth, flags, stream); conv2d: no Cout / kdepth
+    conv2d: bool
+    xdiv: float       # algorithmic / executed FLOPs (Winograd F(2x2, 3x3): 36 / 16 products per output patch)
+
+
+_FORMS = (
+    _Form("c8", "w_c8", False, False, True, lambda L, D, H, W: use_c8, "dmvs_conv2d_c8", True, 1.0),
+    _Form("zmarch", "w_zmarch", False, False, False, lambda L, D, H, W: use_zmarch and use_wino and D >= ZMARCH_MIN_DEPTH,
+          "dmvs_conv3d_zmarch", False, 2.25),
+    _Form("coarse", "w_coarse", False, False, False, lambda L, D, H, W: use_coarse and use_wino, "dmvs_conv3d_coarse", False, 2.25),
+    # (the plan is negative for W % 4 != 0: `auto` skips K3w there; no image stack: K3w reads planar [C][D][H][W] only, ADVICE r04)
+    _Form("wino", "w_wino", False, True, False,
+          lambda L, D, H, W: use_wino and _lib.load().dmvs_conv3d_wino_plan(L.cin, L.cout, D, H, W, L.kdepth) >= WINO_MIN_BLOCKS,
+          "dmvs_conv3d_wino", False, 2.25),
+)
+
+
+def dispatch_key() -> tuple:
+    """Every module switch that steers which kernels a forward launches (MVSNet._forward_graph keys its captured graph on it).
+    use_coarse_feature is not among them: it is read when the weights are packed, not at dispatch."""
+    return (use_c8, use_c8_fused, use_wino, use_coarse, use_zmarch, use_prob_fused, PROB_FUSED_DEPTHS, split_probe,
+            WINO_MIN_BLOCKS, ZMARCH_MIN_DEPTH)
+
+
 def conv3d(x: torch.Tensor, layer: ConvLayer, skip: Optional[torch.Tensor] = None,
            out: Optional[torch.Tensor] = None, backend: str = "auto", skip_up2: bool = False,
            family: Optional[str] = None, out_q4: bool = False, in_views: bool = False) -> torch.Tensor:
     """x [Cin,D,H,W] -> [Cout,Do,Ho,Wo];  y = relu(conv(x)*scale+shift) (+ skip).
     ``out_q4``: the result is written as two quad-planar halves, returned as [2,Do,Cout/8,Ho,Wo,4] (K3 only).
-    ``in_views``: x is the loader's image stack [V,3,H,W], read in place by a 4-channel layer (DMVS_IN_VIEWS)."""
+    ``in_views``: x is the loader's image stack [V,3,H,W], read in place by a 4-channel layer (DMVS_IN_VIEWS).
+    ``backend``: "auto" (the first form of _FORMS that covers the call and accepts it, else K3), "mfma" (K3), "direct" (K2 where
+    the layer has it), a form's name or "split3" / "split6" (the probe): a forced form runs its own kernel or raises."""
     _req(x, skip, out)
     if in_views:
         D, c3, H, W = x.shape
@@ -604,116 +640,47 @@ def conv3d(x: torch.Tensor, layer: ConvLayer, skip: Optional[torch.Tensor] = Non
         assert tuple(skip.shape) == want, (tuple(skip.shape), want)
     if backend in ("split3", "split6") or (split_probe and backend == "auto" and layer.w_split is not None and skip is None
                                            and not out_q4 and not in_views):
+        if skip is not None or out_q4 or in_views:
+            raise _lib.DmvsError(f"layer {layer.name}: the bf16-split probe has no residual, quad-planar output or image-stack input")
         return conv3d_split(x, layer, 3 if backend == "split3" else 6 if backend == "split6" else split_probe, out=out)
+    lib = _lib.load()
+    fam = family or "conv3d_mfma"
+    cin = 3 if in_views else layer.cin
+    flags = (RELU if layer.relu else 0) | (OUT_Q4 if out_q4 else 0) | (IN_VIEWS if in_views else 0)
+    # every form is a stride-1 3x3 conv (make_layer packs them for those layers only): `auto` skips the table for the others
+    for f in _FORMS if (layer.mode == CONV_S1 or backend != "auto") else ():
+        w = getattr(layer, f.weight)
+        forced = backend == f.backend
+        if w is None or (skip is not None and not f.skip) or (out_q4 and not f.q4) or (in_views and not f.views):
+            if forced:
+                raise _lib.DmvsError(f"layer {layer.name}: shape / residual / layout not covered by the {f.backend} kernel")
+            continue
+        if not (forced or (backend == "auto" and f.auto(layer, D, H, W))):
+            continue
+        cost = None
+        if timer is not None:   # FLOPs counted in the direct form (what the layer computes), as for every K3 launch
+            fl = 2.0 * 9 * layer.kdepth * cin * layer.cout * D * H * W
+            # executed: fl / xdiv; conv0 (Cin = 2, K3w) pads its 6 (channel, depth tap) pairs to two k-groups of 4
+            cost = (fl, 4.0 * (cin + layer.cout) * D * H * W, fl / f.xdiv * (8.0 / 6.0 if cin == 2 else 1.0))
+        dims = (cin, D, H, W) if f.conv2d else (cin, layer.cout, D, H, W, layer.kdepth)
+        if _launch(getattr(lib, f.entry), (_ptr(x), _ptr(out), _ptr(w), _ptr(layer.scale), _ptr(layer.shift), *dims, flags),
+                   layer.name, f.backend, x, (w, layer.scale, layer.shift), not forced, fam, cost):
+            return out
     use_mfma = layer.w_mfma is not None and (backend in ("auto", "mfma") or layer.w_direct is None)
     if backend == "mfma" and layer.w_mfma is None:
         raise _lib.DmvsError(f"layer {layer.name}: shape not covered by the MFMA kernel")
-    lib = _lib.load()
-    if backend == "c8" and layer.w_c8 is None:
-        raise _lib.DmvsError(f"layer {layer.name}: not one of the 8-channel layers of the row-sweep kernel")
-    if layer.w_c8 is not None and skip is None and not out_q4 and (backend == "c8" or (backend == "auto" and use_c8)):
-        for t in (layer.w_c8, layer.scale, layer.shift):
-            if t is not None and t.device != x.device:
-                raise _lib.DmvsError(f"layer {layer.name}: weights on {t.device}, activations on {x.device}")
-        cin = 3 if in_views else layer.cin
-        t0 = timer.begin() if timer is not None else None
-        code = lib.dmvs_conv2d_c8(_ptr(x), _ptr(out), _ptr(layer.w_c8), _ptr(layer.scale), _ptr(layer.shift), cin, D, H, W,
-                                  (RELU if layer.relu else 0) | (IN_VIEWS if in_views else 0), _stream())
-        if code == 0:
-            fam = family or "conv3d_mfma"
-            _log(fam)
-            if t0 is not None:
-                timer.end(fam, t0, 2.0 * 9 * cin * 8 * D * H * W, 4.0 * (cin + 8) * D * H * W, label=layer.name)
-            return out
-        if code != _lib.EUNSUPPORTED or backend == "c8":
-            _lib.check(code, f"conv3d[{layer.name}, c8]")
-        if t0 is not None:
-            timer._pool.append(t0)   # beyond the kernel's offset range: the K3 kernel below runs instead
-    if backend == "zmarch" and (layer.w_zmarch is None or skip is not None or out_q4 or in_views):
-        raise _lib.DmvsError(f"layer {layer.name}: shape / residual / layout not covered by the z-marching kernel")
-    if layer.w_zmarch is not None and skip is None and not out_q4 and not in_views and (
-            backend == "zmarch" or (backend == "auto" and use_zmarch and use_wino and D >= ZMARCH_MIN_DEPTH)):
-        for t in (layer.w_zmarch, layer.scale, layer.shift):
-            if t is not None and t.device != x.device:
-                raise _lib.DmvsError(f"layer {layer.name}: weights on {t.device}, activations on {x.device}")
-        t0 = timer.begin() if timer is not None else None
-        code = lib.dmvs_conv3d_zmarch(_ptr(x), _ptr(out), _ptr(layer.w_zmarch), _ptr(layer.scale), _ptr(layer.shift),
-                                      layer.cin, layer.cout, D, H, W, layer.kdepth, RELU if layer.relu else 0, _stream())
-        if code == 0:
-            fam = family or "conv3d_mfma"
-            _log(fam)
-            if t0 is not None:
-                fl = 2.0 * 9 * layer.kdepth * layer.cin * layer.cout * D * H * W
-                timer.end(fam, t0, fl, 4.0 * (layer.cin + layer.cout) * D * H * W, fl / 2.25, label=layer.name)
-            return out
-        if code != _lib.EUNSUPPORTED or backend == "zmarch":
-            _lib.check(code, f"conv3d[{layer.name}, zmarch]")
-        if t0 is not None:
-            timer._pool.append(t0)   # W % 4 != 0 / unaligned / too large: K3w or K3 below
-    if backend == "coarse" and (layer.w_coarse is None or skip is not None or out_q4 or in_views):
-        raise _lib.DmvsError(f"layer {layer.name}: shape / residual / layout not covered by the register-stationary kernel")
-    if layer.w_coarse is not None and skip is None and not out_q4 and not in_views and (
-            backend == "coarse" or (backend == "auto" and use_coarse and use_wino)):
-        for t in (layer.w_coarse, layer.scale, layer.shift):
-            if t is not None and t.device != x.device:
-                raise _lib.DmvsError(f"layer {layer.name}: weights on {t.device}, activations on {x.device}")
-        t0 = timer.begin() if timer is not None else None
-        code = lib.dmvs_conv3d_coarse(_ptr(x), _ptr(out), _ptr(layer.w_coarse), _ptr(layer.scale), _ptr(layer.shift),
-                                      layer.cin, layer.cout, D, H, W, layer.kdepth, RELU if layer.relu else 0, _stream())
-        if code == 0:
-            fam = family or "conv3d_mfma"
-            _log(fam)
-            if t0 is not None:
-                fl = 2.0 * 9 * layer.kdepth * layer.cin * layer.cout * D * H * W
-                timer.end(fam, t0, fl, 4.0 * (layer.cin + layer.cout) * D * H * W, fl / 2.25, label=layer.name)
-            return out
-        if code != _lib.EUNSUPPORTED or backend == "coarse":
-            _lib.check(code, f"conv3d[{layer.name}, coarse]")
-        if t0 is not None:
-            timer._pool.append(t0)
-    if backend == "wino" and (layer.w_wino is None or in_views):
-        raise _lib.DmvsError(f"layer {layer.name}: shape / input layout not covered by the Winograd kernel")
-    # (in_views: K3w reads planar [C][D][H][W] only -- the image stack would be misread)
-    if layer.w_wino is not None and skip is None and not in_views and (backend == "wino" or (
-            backend == "auto" and use_wino
-            and lib.dmvs_conv3d_wino_plan(layer.cin, layer.cout, D, H, W, layer.kdepth) >= WINO_MIN_BLOCKS)):
-        if layer.w_wino.device != x.device:
-            raise _lib.DmvsError(f"layer {layer.name}: weights on {layer.w_wino.device}, activations on {x.device}")
-        t0 = timer.begin() if timer is not None else None
-        code = lib.dmvs_conv3d_wino(_ptr(x), _ptr(out), _ptr(layer.w_wino), _ptr(layer.scale), _ptr(layer.shift),
-                                    layer.cin, layer.cout, D, H, W, layer.kdepth,
-                                    (RELU if layer.relu else 0) | (OUT_Q4 if out_q4 else 0), _stream())
-        if code == 0:
-            fam = family or "conv3d_mfma"
-            _log(fam)
-            if t0 is not None:   # FLOPs counted in the direct form (what the layer computes), as for every K3 launch
-                fl = 2.0 * 9 * layer.kdepth * layer.cin * layer.cout * D * H * W
-                # executed: 16 of 36 products; conv0 (Cin = 2) pads its 6 (channel, depth tap) pairs to two k-groups of 4
-                timer.end(fam, t0, fl, 4.0 * (layer.cin + layer.cout) * D * H * W, fl / 2.25 * (8.0 / 6.0 if layer.cin == 2 else 1.0),
-                          label=layer.name)
-            return out
-        if code != _lib.EUNSUPPORTED or backend == "wino":
-            _lib.check(code, f"conv3d[{layer.name}, wino]")
-        if t0 is not None:
-            timer._pool.append(t0)   # shape / alignment not covered: the direct-form kernel below runs instead
-    fn = lib.dmvs_conv3d_mfma if use_mfma else lib.dmvs_conv3d_direct
     w = layer.w_mfma if use_mfma else layer.w_direct
-    for t in (w, layer.scale, layer.shift):   # raw pointers go to the kernel: a weight left on the CPU / another GPU faults
-        if t is not None and t.device != x.device:
-            raise _lib.DmvsError(f"layer {layer.name}: weights on {t.device}, activations on {x.device}")
-    t0 = timer.begin() if timer is not None else None
-    code = fn(_ptr(x), _ptr(out), _ptr(w), _ptr(layer.scale), _ptr(layer.shift), _ptr(skip), layer.cin, layer.cout,
-              D, H, W, layer.mode, layer.kdepth,
-              (RELU if layer.relu else 0) | (SKIP_UP2 if skip_up2 else 0) | (OUT_Q4 if out_q4 else 0)
-              | (IN_VIEWS if in_views else 0), _stream())
-    _lib.check(code, f"conv3d[{layer.name}, {'mfma' if use_mfma else 'direct'}]")
-    fam = family or ("conv3d_mfma" if use_mfma else ("prob_head" if layer.cout == 2 else "conv3d_direct"))
-    _log(fam)
-    if t0 is not None:
+    cost = None
+    if timer is not None:
         taps = 25 if layer.mode == CONV2D_K5S2 else (1 if layer.mode == CONV2D_K1 else 9 * layer.kdepth)
         vox = D * H * W if layer.mode == DECONV_S2 else Do * Ho * Wo   # deconv: MACs counted on the input grid
         nbytes = 4.0 * (layer.cin * D * H * W + layer.cout * Do * Ho * Wo * (2 if skip is not None else 1))
-        timer.end(fam, t0, 2.0 * taps * layer.cin * layer.cout * vox, nbytes, label=layer.name)
+        cost = (2.0 * taps * layer.cin * layer.cout * vox, nbytes, None)
+    _launch(lib.dmvs_conv3d_mfma if use_mfma else lib.dmvs_conv3d_direct,
+            (_ptr(x), _ptr(out), _ptr(w), _ptr(layer.scale), _ptr(layer.shift), _ptr(skip), layer.cin, layer.cout, D, H, W,
+             layer.mode, layer.kdepth, flags | (SKIP_UP2 if skip_up2 else 0)),
+            layer.name, "mfma" if use_mfma else "direct", x, (w, layer.scale, layer.shift), False,
+            family or ("conv3d_mfma" if use_mfma else ("prob_head" if layer.cout == 2 else "conv3d_direct")), cost)
     return out
 
 
@@ -728,27 +695,17 @@ def conv3d_fpn(lat: torch.Tensor, td: torch.Tensor, layer: ConvLayer, out_q4: bo
     assert tuple(td.shape) == (Cin, V, H // 2, W // 2) and layer.cin == Cin
     if not use_wino or layer.w_wino_fpn is None or (Cl, Cin, layer.cout) != (8, 32, 16):
         return None
-    for t in (layer.w_wino_fpn, layer.scale, layer.shift):
-        if t is not None and t.device != lat.device:
-            raise _lib.DmvsError(f"layer {layer.name}: weights on {t.device}, activations on {lat.device}")
     oshape = (2, V, layer.cout // 8, H, W, 4) if out_q4 else (layer.cout, V, H, W)
     out = torch.empty(oshape, dtype=torch.float32, device=lat.device)
-    t0 = timer.begin() if timer is not None else None
-    code = _lib.load().dmvs_conv3d_wino_fpn2(_ptr(lat), _ptr(td), _ptr(_ones_hw(layer, H, W, lat.device)), _ptr(out),
-                                             _ptr(layer.w_wino_fpn), _ptr(layer.scale), _ptr(layer.shift), V, H, W,
-                                             (RELU if layer.relu else 0) | (OUT_Q4 if out_q4 else 0), _stream())
-    if code == _lib.EUNSUPPORTED:
-        if t0 is not None:
-            timer._pool.append(t0)
+    vox = V * H * W
+    # executed: (3 x 16 + 8 x 9) MFMAs of 2048 FLOP per 64 pixels
+    cost = (2.0 * vox * (9 * Cin * layer.cout + Cl * Cin), 4.0 * (Cl * vox + Cin * vox / 4 + layer.cout * vox), vox * 120 * 2048 / 64.0)
+    if not _launch(_lib.load().dmvs_conv3d_wino_fpn2,
+                   (_ptr(lat), _ptr(td), _ptr(_ones_hw(layer, H, W, lat.device)), _ptr(out), _ptr(layer.w_wino_fpn), _ptr(layer.scale),
+                    _ptr(layer.shift), V, H, W, (RELU if layer.relu else 0) | (OUT_Q4 if out_q4 else 0)),
+                   layer.name, "conv3d_fpn", lat, (layer.w_wino_fpn, layer.scale, layer.shift), True, family or "conv3d_mfma",
+                   cost, label="feature.out3.fpn"):
         return None
-    _lib.check(code, f"conv3d_fpn[{layer.name}]")
-    _log(family or "conv3d_mfma")
-    if t0 is not None:
-        vox = V * H * W
-        fl = 2.0 * vox * (9 * Cin * layer.cout + Cl * Cin)
-        # executed: (3 x 16 + 8 x 9) MFMAs of 2048 FLOP per 64 pixels
-        timer.end(family or "conv3d_mfma", t0, fl, 4.0 * (Cl * vox + Cin * vox / 4 + layer.cout * vox), vox * 120 * 2048 / 64.0,
-                  label="feature.out3.fpn")
     return out
 
 
@@ -774,22 +731,12 @@ def prob_regress(x: torch.Tensor, layer: ConvLayer, depth_dhw, interval: torch.T
                              "from the planes K1 correlated")
     Cin, D, H, W = x.shape
     assert layer.cout == 2 and Cin == layer.cin and tuple(out.shape) == (2, H, W) and tuple(depth_dhw.shape) == (D, H, W)
-    if layer.w_direct.device != x.device:
-        raise _lib.DmvsError(f"layer {layer.name}: weights on {layer.w_direct.device}, activations on {x.device}")
-    t0 = timer.begin() if timer is not None else None
-    code = _lib.load().dmvs_prob_regress(_ptr(x), _ptr(layer.w_direct), Cin, D, H, W, None if affine else _ptr(depth_dhw),
-                                         _ptr(depth_dhw.base) if affine else None, _ptr(interval) if affine else None,
-                                         float(alpha), _ptr(out), _stream())
-    if code == _lib.EUNSUPPORTED:
-        if t0 is not None:
-            timer._pool.append(t0)
-        return False
-    _lib.check(code, f"prob_regress[{layer.name}]")
-    _log("prob_head")
-    if t0 is not None:
-        hyp = H * W if affine else D * H * W
-        timer.end("prob_head", t0, 2.0 * 27 * Cin * 2 * D * H * W, 4.0 * (Cin * D * H * W + hyp + 2 * H * W), label=layer.name)
-    return True
+    hyp = H * W if affine else D * H * W
+    cost = None if timer is None else (2.0 * 27 * Cin * 2 * D * H * W, 4.0 * (Cin * D * H * W + hyp + 2 * H * W), None)
+    return _launch(_lib.load().dmvs_prob_regress, (_ptr(x), _ptr(layer.w_direct), Cin, D, H, W, None if affine else _ptr(depth_dhw),
+                                                   _ptr(depth_dhw.base) if affine else None, _ptr(interval) if affine else None,
+                                                   float(alpha), _ptr(out)),
+                   layer.name, "prob_regress", x, (layer.w_direct,), True, "prob_head", cost)
 
 
 def depth_select(dsp: torch.Tensor, interval: torch.Tensor, mode: int):

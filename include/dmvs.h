@@ -76,7 +76,6 @@ int dmvs_version(void);
  *   "c8_rows"                   rows per wave of the K3s row sweep (0 = chosen from the wave count)
  *   "k3z_grid"                  persistent workgroups of a K3z launch (dmvs_conv3d_zmarch; multiple of 8, 0 = as many as are resident)
  *   "k3z_zs"                    cap of a z segment's length in K3z (0 = none; results do not depend on it)
- *   "k3z_counted_wait"          ring of 3 builds only: 1 = counted vmcnt at the stage wait, 0 = vmcnt(0)
  * Returns 0, DMVS_EINVAL (bad value) or DMVS_EUNSUPPORTED (unknown name).  Process-wide, not thread-safe. */
 int dmvs_tune(const char* name, int value);
 const char* dmvs_error_string(int code);
@@ -247,7 +246,7 @@ int dmvs_pack_conv_weights_coarse(const float* w /* [Cout][Cin][kd][3][3] */, fl
 /* K3z: conv2 of the regularisation nets (module.py:364, 406: Conv3d 16 -> 16, 3x3x3, stride 1) in Winograd F(2x2, 3x3) form with
  * register-stationary filters, marching along z (csrc/conv3d_zmarch.hip): a 256-thread workgroup = the 4 transform rows, each
  * wave keeps its share of G g G^T for all 3 depth taps in VGPRs; one pipeline stage = one input plane of an 8 x 8-output column,
- * transformed once and used as depth tap 0 / 1 / 2 of three output planes; 3 persistent workgroups per CU.
+ * transformed once and used as depth tap 0 / 1 / 2 of three output planes; 2 persistent workgroups per CU.
  *   out = relu(conv(in) * scale + shift), in [16][D][H][W], out [16][D][H][W].  flags: DMVS_RELU.
  *   w_packed: dmvs_pack_conv_weights_zmarch (host); dmvs_conv3d_zmarch_weight_floats = its length, 0 for a shape not compiled
  *   (only (16, 16, kdepth 3)).  Needs W % 4 == 0 and 16-byte aligned tensors.

@@ -760,7 +760,7 @@ def _net(ndepths, ratios, seed, inverse=False):
     return net.to(DEV), sd
 
 
-@pytest.mark.parametrize("backend", ["direct", "auto"])
+@pytest.mark.parametrize("backend", ["direct", "auto", "mfma"])
 def test_costreg_golden(golden, backend):
     g = golden("op_costreg.npz")
     net, _ = _net([8], [4], int(g["seed"]))
@@ -1413,6 +1413,20 @@ def test_graph_replay_matches_eager():
         outs[seed] = got["depth"]
     assert outs[1] is outs[2]          # same shape: same static output (overwritten by the replay)
     assert outs[3] is not outs[2]      # new shape: new capture
+    # a dispatch switch toggled between two calls of one shape: a new capture, equal to the eager forward under the new setting
+    saved = ops.use_wino
+    try:
+        ops.use_wino = False
+        net.use_graph = False
+        eager = {k: v.clone() for k, v in net(*args).items() if torch.is_tensor(v)}
+        net.use_graph = True
+        got = net(*args)
+        torch.cuda.synchronize()
+    finally:
+        ops.use_wino = saved
+    assert got["depth"] is not outs[3]
+    for k, v in eager.items():
+        assert torch.equal(got[k], v), k
 
 
 # ------------------------------------------------------------------------------------------ N2: affine hypotheses
