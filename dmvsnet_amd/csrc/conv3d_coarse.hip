@@ -32,6 +32,7 @@
 // W % 4 != 0 (the 37 x 50 volumes of config 2's stage 1): dword LDS-direct loads (4x the load instructions).
 #include "common.h"
 #include "tile_loader.h"
+#include "wino.h"
 
 #include <algorithm>
 
@@ -62,9 +63,6 @@ long g_k3r_grid = 256;
 long g_k3r_counted_wait = 1;
 
 namespace {
-
-typedef float acc4_t __attribute__((ext_vector_type(4)));
-typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
 
 struct CoarseArgs {
     const float* in;
@@ -109,7 +107,8 @@ template <int KD, int CIN, int NCB, bool V4>
 __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
     typedef CoarseGeom<KD, CIN, NCB, V4> G;
     constexpr int NST = G::NST, GPH = G::GPH, RING = G::RING, IXP = G::IXP, PS = G::PS, PF = G::PF, NS = G::NS, LW = G::LW;
-    constexpr unsigned kInvalid = 0x80000000u;
+    constexpr unsigned kInvalid = kWinoInvalid;
+    typedef ByteRange<3> ZYX;   // the loader's range test of a piece's (plane, row, x)
     extern __shared__ __attribute__((aligned(16))) float smem[];   // [RING][STAGE_F] tiles, [EX_F] exchange
     float* const ex = smem + RING * G::STAGE_F;
 
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
         const bool okp = qi < G::NI && c < G::CPS && rem < KD * G::PLANE;
         const int row = rem / IXP, x = rem - row * IXP, z = row / G::IY, y = row - z * G::IY;
         roff[sl] = c * vol + z * plane + y * a.W + x;
-        zyx[sl] = okp ? (unsigned)(z | (y << 8) | (x << 16)) : 0x3f3f3fu;   // a pad piece fails every range test below
+        zyx[sl] = okp ? ZYX::pack(z, y, x) : ZYX::kNever;   // a pad piece fails every range test below
     }
     // one descriptor for the whole tensor; an invalid piece gets offset 2^31 (+- the unit's base): out of range either way
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, (short)0, CIN * vol * 4, 0x00020000);
@@ -180,21 +179,18 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
         if (++sq == NST) { sq = 0; ++jq; }
         const int zb = oz - (KD == 3 ? 1 : 0), yb = oy0 - 1, xb = ox0 - 4;
         q_ubase4 = (unsigned)(s * G::CPS * vol + zb * plane + yb * a.W + xb) * 4u;
-        // valid tile coordinates of this unit, [lo, hi] per axis (uniform); the lane's (z, y, x) bytes are range-checked together:
-        // with the guard bit 7 set, a byte-wise subtraction keeps the guard iff it did not borrow
+        // valid tile coordinates of this unit, [lo, hi] per axis (uniform); the lane's (z, y, x) bytes are range-checked together
         const unsigned zl = max(0, -zb), yl = max(0, -yb), xl = max(0, -xb);
         const unsigned zh = min(KD, a.D - zb) - 1, yh = min(G::IY, a.H - yb) - 1, xh = min(IXP, a.W - xb) - 1;
-        q_LO = on ? (zl | (yl << 8) | (xl << 16)) : 0x7f7f7fu;   // off: no coordinate is >= 127
-        q_HG = (zh | (yh << 8) | (xh << 16)) | 0x808080u;
+        q_LO = on ? ZYX::pack(zl, yl, xl) : ZYX::kNothing;   // off: no coordinate is >= 127
+        q_HG = ZYX::pack_hi(zh, yh, xh);
         q_dst = smem + ring_q * G::STAGE_F + (wave & (LW - 1)) * 64 * PF;
         ring_q = ring_q + 1 == RING ? 0 : ring_q + 1;
     };
     const bool loader = LW == 8 || th == 1;
     auto issue_slot = [&](int sl) {
         if (!loader) return;
-        const unsigned ge = (zyx[sl] | 0x808080u) - q_LO, le = q_HG - zyx[sl];
-        const bool ok = (ge & le & 0x808080u) == 0x808080u;
-        const unsigned off = ok ? q_ubase4 + (unsigned)roff[sl] * 4u : kInvalid;
+        const unsigned off = ZYX::in_range(zyx[sl], q_LO, q_HG) ? q_ubase4 + (unsigned)roff[sl] * 4u : kInvalid;
         if constexpr (V4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(q_dst + sl * LW * 64 * 4), 16, off, 0, 0, 0);
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(q_dst + sl * LW * 64), 4, off, 0, 0, 0);
     };
@@ -232,11 +228,11 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
 #pragma unroll
         for (int rs = 0; rs < 2; ++rs) {
             if (frr == 0) {
-                y[2 * rs] = (P[0][rs].x + P[1][rs].x) + P[2][rs].x;
-                y[2 * rs + 1] = (P[0][rs].y + P[1][rs].y) + P[2][rs].y;
+                y[2 * rs] = wino_at0(P[0][rs].x, P[1][rs].x, P[2][rs].x);
+                y[2 * rs + 1] = wino_at0(P[0][rs].y, P[1][rs].y, P[2][rs].y);
             } else {
-                y[2 * rs] = (P[1][rs].x - P[2][rs].x) - P[3][rs].x;
-                y[2 * rs + 1] = (P[1][rs].y - P[2][rs].y) - P[3][rs].y;
+                y[2 * rs] = wino_at1(P[1][rs].x, P[2][rs].x, P[3][rs].x);
+                y[2 * rs + 1] = wino_at1(P[1][rs].y, P[2][rs].y, P[3][rs].y);
             }
         }
         const int x = ox0 + 4 * fxh, yy = oy0 + 2 * lk + frr;
@@ -244,16 +240,15 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
         const unsigned pos = (unsigned)(co_f * vol + oz * plane + yy * a.W + x) * 4u;
         if (a.st4) {
             v4u_t qv;
-            qv.x = __builtin_bit_cast(unsigned, fmaxf(y[0] * bsc + bsh, lo));
-            qv.y = __builtin_bit_cast(unsigned, fmaxf(y[1] * bsc + bsh, lo));
-            qv.z = __builtin_bit_cast(unsigned, fmaxf(y[2] * bsc + bsh, lo));
-            qv.w = __builtin_bit_cast(unsigned, fmaxf(y[3] * bsc + bsh, lo));
-            __builtin_amdgcn_raw_buffer_store_b128(qv, rs_out, (rok && x < a.W) ? pos : kInvalid, 0, 0);
-        } else {
+            qv.x = wino_bn_relu(y[0], bsc, bsh, lo);
+            qv.y = wino_bn_relu(y[1], bsc, bsh, lo);
+            qv.z = wino_bn_relu(y[2], bsc, bsh, lo);
+            qv.w = wino_bn_relu(y[3], bsc, bsh, lo);
+            wino_store16<false>(rs_out, qv, (rok && x < a.W) ? pos : kInvalid);
+        } else {   // W % 4 != 0: a piece may straddle the row end, four 4-byte stores
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fmaxf(y[e] * bsc + bsh, lo)), rs_out,
-                                                      (rok && x + e < a.W) ? pos + 4u * e : kInvalid, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(wino_bn_relu(y[e], bsc, bsh, lo), rs_out, (rok && x + e < a.W) ? pos + 4u * e : kInvalid, 0, 0);
         }
     };
 
@@ -306,19 +301,18 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
             for (int st = 0; st < NSTEP; ++st) {
                 const int gg = st / KD, kz = st - gg * KD;
                 const int o = gg * 4 * PS + kz * G::PLANE;
-                const float2_t a0 = *reinterpret_cast<const float2_t*>(pa + o), a1 = *reinterpret_cast<const float2_t*>(pa + o + 2),
-                               a2 = *reinterpret_cast<const float2_t*>(pa + o + 4);
-                const float2_t b0 = *reinterpret_cast<const float2_t*>(pb + o), b1 = *reinterpret_cast<const float2_t*>(pb + o + 2),
-                               b2 = *reinterpret_cast<const float2_t*>(pb + o + 4);
-                const float t0 = fmaf(sg, b0.y, a0.y), t1 = fmaf(sg, b1.x, a1.x), t2 = fmaf(sg, b1.y, a1.y), t3 = fmaf(sg, b2.x, a2.x);
-                const float v0 = t0 - t2, v1 = t1 + t2, v2 = t2 - t1, v3 = t1 - t3;
+                float2_t rd[6];
+                wino_read_pairs(pa + o, rd);
+                wino_read_pairs(pb + o, rd + 3);
+                float v[4];
+                wino_in_row(sg, rd, v);
 #pragma unroll
                 for (int nb = 0; nb < NCB; ++nb) {
                     const float4_t wv = w[((s * GPH + gg) * KD + kz) * NCB + nb];
-                    acc[nb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v0, wv.x, acc[nb][0], 0, 0, 0);
-                    acc[nb][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v1, wv.y, acc[nb][1], 0, 0, 0);
-                    acc[nb][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(v2, wv.z, acc[nb][2], 0, 0, 0);
-                    acc[nb][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(v3, wv.w, acc[nb][3], 0, 0, 0);
+                    acc[nb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[0], wv.x, acc[nb][0], 0, 0, 0);
+                    acc[nb][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[1], wv.y, acc[nb][1], 0, 0, 0);
+                    acc[nb][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[2], wv.z, acc[nb][2], 0, 0, 0);
+                    acc[nb][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[3], wv.w, acc[nb][3], 0, 0, 0);
                 }
                 if (st == FIN_AT && fin_now) finish_store(pox, poy, poz);
 #pragma unroll
@@ -337,13 +331,7 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
 #pragma unroll
         for (int nb = 0; nb < NCB; ++nb)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float m0 = acc[nb][0][r], m1 = acc[nb][1][r], m2 = acc[nb][2][r], m3 = acc[nb][3][r];
-                float2_t sv;
-                sv.x = (m0 + m1) + m2;
-                sv.y = (m1 - m2) - m3;
-                exw[(nb * 4 + r) * 64] = sv;
-            }
+            for (int r = 0; r < 4; ++r) exw[(nb * 4 + r) * 64] = wino_out_half(acc[nb][0][r], acc[nb][1][r], acc[nb][2][r], acc[nb][3][r]);
         R_ACC(4);
         pox = ox0; poy = oy0; poz = oz;
     }

@@ -11,8 +11,7 @@
 // result differs at re-association level (measured in tests/test_gpu_parity.py::test_conv3d_wino: <= 2e-5 of the
 // layer's output scale, the tolerance of the direct kernels' own tests).
 //
-//   Y = A^T [ sum_{ci,kz} (G g G^T) .* (B^T d B) ] A          per 2x2 output patch ("tile"), d = its 4x4 input patch
-//   B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]   G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]   A^T = [1 1 1 0; 0 1 -1 -1]
+// The transforms (B^T d B, A^T M A), the store epilogue and the persistent tile walk are in wino.h, with the matrices.
 //
 // GEMM view: for each of the 16 transform positions xi, M_xi[tile][cout] = sum_{kz, ci} V_xi[tile][kz, ci] * U_xi[kz, ci][cout]
 //   -> 16 independent accumulators per (16 tiles x 16 couts) block, v_mfma_f32_16x16x4_f32 with the tiles as rows
@@ -33,11 +32,9 @@
 #ifndef DMVS_WKO
 #define DMVS_WKO 0
 #endif
-#ifndef DMVS_WINO_TAU
-#define DMVS_WINO_TAU 0   /* tile permutation for 64-byte store runs: measured neutral (same-box A/B), off */
-#endif
 #include "common.h"
 #include "tile_loader.h"
+#include "wino.h"
 #include "dev_guard.h"
 
 #include <algorithm>
@@ -47,13 +44,12 @@
 extern long g_wino_stages, g_wino_persistent, g_wino_conv0_grid;
 namespace {
 
-typedef float acc4_t __attribute__((ext_vector_type(4)));
+constexpr bool kNoStores = (DMVS_WKO & 4) != 0;   // development knock-out of the output stores
 #if DMVS_WKO & 2
 __device__ __forceinline__ acc4_t wino_mfma(float a, float b, acc4_t c) { c.x += a + b; return c; }
 #else
 __device__ __forceinline__ acc4_t wino_mfma(float a, float b, acc4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 #endif
-typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
 
 struct WinoArgs {
     const float* in;
@@ -105,7 +101,7 @@ template <int KD, int MB, int MBW, int TZ, int TRW, int GPC, bool Q4 = false>
 __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
     typedef WinoGeom<KD, MB, MBW, TZ, TRW, GPC> G;
     constexpr int IY = G::IY, IZ = G::IZ, IXP = G::IXP, PS = G::PS, NTR = G::NTR;
-    constexpr unsigned kInvalid = 0x80000000u;
+    constexpr unsigned kInvalid = kWinoInvalid;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // [1 or 2][BUF_F]
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -113,17 +109,15 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
     const int ln = lane & 15, lk = lane >> 4;
     const int trg = wave % NTR, mg = wave / NTR;   // the wave's tile-row group and output-channel group
 
-    // PERSISTENT workgroups: a workgroup walks the tiles vb = blockIdx.x, + gridDim.x, ... of the XCD-aware tile list
-    // (common.h: XCD k owns the k-th contiguous eighth; gridDim.x is a multiple of 8, so vb % 8 stays the workgroup's
-    // XCD).  The (tile, chunk) pairs form ONE pipeline: the first chunk of the next tile is staged before the epilogue of
-    // the current one, so a tile's first-load latency, the kernel-argument / BatchNorm loads and the store tail of the
-    // previous tile are off the MFMA path (r03 knock-outs: with one tile per workgroup these fixed ~5 us per workgroup
-    // cost a third of the kernel).
+    // PERSISTENT workgroups (XcdTileWalk, wino.h).  The (tile, chunk) pairs form ONE pipeline: the first chunk of the next
+    // tile is staged before the epilogue of the current one, so a tile's first-load latency, the kernel-argument / BatchNorm
+    // loads and the store tail of the previous tile are off the MFMA path (r03 knock-outs: with one tile per workgroup
+    // these fixed ~5 us per workgroup cost a third of the kernel).
     struct Tile { int ox0, oy0, oz0; };
-    const int ntiles = a.nx * a.ny * a.nz, per_xcd = (ntiles + 7) >> 3;
-    auto tile_of = [&](int vb, Tile& t) {
-        const int q = vb >> 3, id = (vb & 7) * per_xcd + q;
-        if (q >= per_xcd || id >= ntiles) return false;
+    const XcdTileWalk walk(a.nx * a.ny * a.nz);
+    auto tile_of = [&](int vb, Tile& t) {   // tile list order: x, z, y for the 3D layers (the depth halo is the largest), else x, y, z
+        int id;
+        if (!walk.id_of(vb, id)) return false;
         const int bx = id % a.nx, r = id / a.nx;
         int by, bz;
         if (KD == 3) { bz = r % a.nz; by = r / a.nz; } else { by = r % a.ny; bz = r / a.ny; }
@@ -137,12 +131,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
     // The lane's patch of tile n (output columns 2n, 2n+1) spans tile columns 3 + 2n .. 6 + 2n: read as the three aligned
     // pairs starting at 2 + 2n.  ds_read_b64 is served in two 32-lane groups with bank = dword address mod 64: the 16
     // tiles of one channel cover 32 consecutive banks, the second channel of the group sits PS = 32 (mod 64) further.
-    // Planar output: MFMA row i is tile tau(i) = (i & 2 ? 8 : 0) + 2 * (i >> 2) + (i & 1), so that the 4 accumulator rows of a
-    // lane (i = 4 lk + r) are the tile pairs {2 lk, 2 lk + 1} and {8 + 2 lk, 9 + 2 lk}: its two 16-byte pieces per row, and
-    // the pieces of the 4 lk-lanes of a channel are CONTIGUOUS in each store instruction (64-byte runs instead of 16-byte
-    // pieces at a 32-byte stride).  A permutation inside the 16-lane group: the patch reads stay conflict-free.
-    const int tau = (Q4 || !DMVS_WINO_TAU) ? ln : ((ln & 2) ? 8 : 0) + 2 * (ln >> 2) + (ln & 1);
-    const int pbase = lk * PS + (2 * TRW * trg) * IXP + 2 + 2 * tau;
+    const int pbase = lk * PS + (2 * TRW * trg) * IXP + 2 + 2 * ln;
 
     const int in_vol = a.D * a.H * a.W;
     const int nchunks = a.Cin / G::CI_CH;
@@ -216,27 +205,14 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
                             for (int y = 0; y < 4; ++y)
 #pragma unroll
                                 for (int x = 0; x < 4; ++x) d[y][x] = (float)(lane + y * 4 + x + pz);
-                        } else
-#pragma unroll
-                        for (int y = 0; y < 4; ++y) {
-                            const float2_t q0 = *reinterpret_cast<const float2_t*>(p + y * IXP);
-                            const float2_t q1 = *reinterpret_cast<const float2_t*>(p + y * IXP + 2);
-                            const float2_t q2 = *reinterpret_cast<const float2_t*>(p + y * IXP + 4);
-                            d[y][0] = q0.y; d[y][1] = q1.x; d[y][2] = q1.y; d[y][3] = q2.x;
+                        } else {
+                            wino_read_patch(p, IXP, d);
                         }
                         float v[16];
 #pragma unroll
-                        for (int x = 0; x < 4; ++x) {   // B^T d (rows), then (.) B (columns)
-                            const float t0 = d[0][x] - d[2][x], t1 = d[1][x] + d[2][x], t2 = d[2][x] - d[1][x], t3 = d[1][x] - d[3][x];
-                            d[0][x] = t0; d[1][x] = t1; d[2][x] = t2; d[3][x] = t3;
-                        }
+                        for (int x = 0; x < 4; ++x) wino_bt4(d[0][x], d[1][x], d[2][x], d[3][x], d[0][x], d[1][x], d[2][x], d[3][x]);   // B^T d
 #pragma unroll
-                        for (int y = 0; y < 4; ++y) {
-                            v[4 * y + 0] = d[y][0] - d[y][2];
-                            v[4 * y + 1] = d[y][1] + d[y][2];
-                            v[4 * y + 2] = d[y][2] - d[y][1];
-                            v[4 * y + 3] = d[y][1] - d[y][3];
-                        }
+                        for (int y = 0; y < 4; ++y) wino_bt4(d[y][0], d[y][1], d[y][2], d[y][3], v[4 * y], v[4 * y + 1], v[4 * y + 2], v[4 * y + 3]);   // (.) B
 #pragma unroll
                         for (int oz = 0; oz < TZ; ++oz) {
                             const int kz = KD == 3 ? pz - oz : 0;
@@ -278,19 +254,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
                     for (int t = 0; t < TRW; ++t) {
                         float y[4][2][2];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float s0[4], s1[4];
-#pragma unroll
-                            for (int b = 0; b < 4; ++b) {
-                                const float m0 = acc[oz][t][mb][b][r], m1 = acc[oz][t][mb][4 + b][r], m2 = acc[oz][t][mb][8 + b][r], m3 = acc[oz][t][mb][12 + b][r];
-                                s0[b] = (m0 + m1) + m2;
-                                s1[b] = (m1 - m2) - m3;
-                            }
-                            y[r][0][0] = (s0[0] + s0[1]) + s0[2];
-                            y[r][0][1] = (s0[1] - s0[2]) - s0[3];
-                            y[r][1][0] = (s1[0] + s1[1]) + s1[2];
-                            y[r][1][1] = (s1[1] - s1[2]) - s1[3];
-                        }
+                        for (int r = 0; r < 4; ++r) wino_out_xform(acc[oz][t][mb], r, y[r][0], y[r][1]);
                         const int oz_g = oz0 + oz;
 #pragma unroll
                         for (int rr = 0; rr < 2; ++rr) {
@@ -299,13 +263,13 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
 #pragma unroll
                             for (int e = 0; e < 2; ++e) {
                                 const int x = ox0 + 2 * ln + e;
-                                v4u_t qv;
-                                qv.x = __builtin_bit_cast(unsigned, fmaxf(y[0][rr][e] * sc[mb][0] + sh[mb][0], lo));
-                                qv.y = __builtin_bit_cast(unsigned, fmaxf(y[1][rr][e] * sc[mb][1 % NCO] + sh[mb][1 % NCO], lo));
-                                qv.z = __builtin_bit_cast(unsigned, fmaxf(y[2][rr][e] * sc[mb][2 % NCO] + sh[mb][2 % NCO], lo));
-                                qv.w = __builtin_bit_cast(unsigned, fmaxf(y[3][rr][e] * sc[mb][3 % NCO] + sh[mb][3 % NCO], lo));
                                 const unsigned off = (unsigned)(((hsel * a.D + oz_g) * cq + cqi) * out_plane + oy * a.W + x) * 16u;
-                                __builtin_amdgcn_raw_buffer_store_b128(qv, rs_out, (rok && x < a.W && !((DMVS_WKO & 4) && qv.x != 0x12345678u)) ? off : kInvalid, 0, 0);
+                                v4u_t qv;
+                                qv.x = wino_bn_relu(y[0][rr][e], sc[mb][0], sh[mb][0], lo);
+                                qv.y = wino_bn_relu(y[1][rr][e], sc[mb][1], sh[mb][1], lo);
+                                qv.z = wino_bn_relu(y[2][rr][e], sc[mb][2], sh[mb][2], lo);
+                                qv.w = wino_bn_relu(y[3][rr][e], sc[mb][3], sh[mb][3], lo);
+                                wino_store16<kNoStores>(rs_out, qv, (rok && x < a.W) ? off : kInvalid);
                             }
                         }
                     }
@@ -321,19 +285,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
                     for (int t = 0; t < TRW; ++t) {
                         float row[2][8];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float s0[4], s1[4];
-#pragma unroll
-                            for (int b = 0; b < 4; ++b) {
-                                const float m0 = acc[oz][t][mb][b][r], m1 = acc[oz][t][mb][4 + b][r], m2 = acc[oz][t][mb][8 + b][r], m3 = acc[oz][t][mb][12 + b][r];
-                                s0[b] = (m0 + m1) + m2;
-                                s1[b] = (m1 - m2) - m3;
-                            }
-                            row[0][2 * r] = (s0[0] + s0[1]) + s0[2];
-                            row[0][2 * r + 1] = (s0[1] - s0[2]) - s0[3];
-                            row[1][2 * r] = (s1[0] + s1[1]) + s1[2];
-                            row[1][2 * r + 1] = (s1[1] - s1[2]) - s1[3];
-                        }
+                        for (int r = 0; r < 4; ++r) wino_out_xform(acc[oz][t][mb], r, row[0] + 2 * r, row[1] + 2 * r);
                         const int oz_g = oz0 + oz;
 #pragma unroll
                         for (int rr = 0; rr < 2; ++rr) {
@@ -341,14 +293,14 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
                             const bool rok = cok && oz_g < a.D && oy < a.H;
 #pragma unroll
                             for (int h = 0; h < 2; ++h) {
-                                const int x = DMVS_WINO_TAU ? ox0 + 16 * h + 4 * lk : ox0 + 8 * lk + 4 * h;   // rows r = 2h, 2h + 1 of the lane: tiles 8h + 2lk, + 1
+                                const int x = ox0 + 8 * lk + 4 * h;   // rows r = 2h, 2h + 1 of the lane: tiles 4 lk + 2h, + 1
                                 const unsigned pos = (unsigned)(co * out_vol + oz_g * out_plane + oy * a.W + x) * 4u;
                                 v4u_t qv;
-                                qv.x = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 0] * sc[mb][0] + sh[mb][0], lo));
-                                qv.y = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 1] * sc[mb][0] + sh[mb][0], lo));
-                                qv.z = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 2] * sc[mb][0] + sh[mb][0], lo));
-                                qv.w = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 3] * sc[mb][0] + sh[mb][0], lo));
-                                __builtin_amdgcn_raw_buffer_store_b128(qv, rs_out, (rok && x < a.W && !((DMVS_WKO & 4) && qv.x != 0x12345678u)) ? pos : kInvalid, 0, 0);
+                                qv.x = wino_bn_relu(row[rr][4 * h + 0], sc[mb][0], sh[mb][0], lo);
+                                qv.y = wino_bn_relu(row[rr][4 * h + 1], sc[mb][0], sh[mb][0], lo);
+                                qv.z = wino_bn_relu(row[rr][4 * h + 2], sc[mb][0], sh[mb][0], lo);
+                                qv.w = wino_bn_relu(row[rr][4 * h + 3], sc[mb][0], sh[mb][0], lo);
+                                wino_store16<kNoStores>(rs_out, qv, (rok && x < a.W) ? pos : kInvalid);
                             }
                         }
                     }
@@ -371,17 +323,17 @@ __global__ __launch_bounds__(256, 2) void conv0_wino_kernel(WinoArgs a) {
     constexpr int TZ = 2, TY = 8, IZ = 4, IY = 10, LPR = 10, IXP = 40;
     constexpr int PS0 = IZ * IY * IXP, PS = PS0 + (32 - PS0 % 64 + 64) % 64;
     constexpr int TILE_F = (2 * PS + 63) & ~63, W_F = 2 * 4 * 256;
-    constexpr unsigned kInvalid = 0x80000000u;
+    constexpr unsigned kInvalid = kWinoInvalid;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // [W_F] weights, [2][TILE_F] tiles
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ln = lane & 15, lk = lane >> 4;
     struct Tile { int ox0, oy0, oz0; };
-    const int ntiles = a.nx * a.ny * a.nz, per_xcd = (ntiles + 7) >> 3;
+    const XcdTileWalk walk(a.nx * a.ny * a.nz);
     auto tile_of = [&](int vb, Tile& t) {
-        const int q = vb >> 3, id = (vb & 7) * per_xcd + q;
-        if (q >= per_xcd || id >= ntiles) return false;
+        int id;
+        if (!walk.id_of(vb, id)) return false;
         const int bx = id % a.nx, r = id / a.nx;
         t.ox0 = bx * 32; t.oz0 = (r % a.nz) * TZ; t.oy0 = (r / a.nz) * TY;
         return true;
@@ -399,8 +351,7 @@ __global__ __launch_bounds__(256, 2) void conv0_wino_kernel(WinoArgs a) {
         load_tile4<2, IZ, IY, LPR, PS>(a.D, a.H, a.W, rs_in, dst, t.oz0 - 1, t.oy0 - 1, t.ox0 - 4, wave, lane);
     };
     // patch of tile ln, channel lk & 1, wave's tile row; the plane is picked per k-step
-    const int tau = !DMVS_WINO_TAU ? ln : ((ln & 2) ? 8 : 0) + 2 * (ln >> 2) + (ln & 1);   // tile of MFMA row ln (see conv_wino_kernel: 64-byte store runs)
-    const int pbase = (lk & 1) * PS + (2 * wave) * IXP + 2 + 2 * tau;
+    const int pbase = (lk & 1) * PS + (2 * wave) * IXP + 2 + 2 * ln;
     const int zsel = lk >> 1;
     const float* wl = smem + lane * 4;
 
@@ -425,26 +376,12 @@ __global__ __launch_bounds__(256, 2) void conv0_wino_kernel(WinoArgs a) {
             for (int st = 0; st < 2; ++st) {
                 const float* p = tile + (oz + (st ? 2 : zsel)) * (IY * IXP);
                 float d[4][4];
-#pragma unroll
-                for (int y = 0; y < 4; ++y) {
-                    const float2_t q0 = *reinterpret_cast<const float2_t*>(p + y * IXP);
-                    const float2_t q1 = *reinterpret_cast<const float2_t*>(p + y * IXP + 2);
-                    const float2_t q2 = *reinterpret_cast<const float2_t*>(p + y * IXP + 4);
-                    d[y][0] = q0.y; d[y][1] = q1.x; d[y][2] = q1.y; d[y][3] = q2.x;
-                }
+                wino_read_patch(p, IXP, d);
                 float v[16];
 #pragma unroll
-                for (int x = 0; x < 4; ++x) {
-                    const float t0 = d[0][x] - d[2][x], t1 = d[1][x] + d[2][x], t2 = d[2][x] - d[1][x], t3 = d[1][x] - d[3][x];
-                    d[0][x] = t0; d[1][x] = t1; d[2][x] = t2; d[3][x] = t3;
-                }
+                for (int x = 0; x < 4; ++x) wino_bt4(d[0][x], d[1][x], d[2][x], d[3][x], d[0][x], d[1][x], d[2][x], d[3][x]);
 #pragma unroll
-                for (int y = 0; y < 4; ++y) {
-                    v[4 * y + 0] = d[y][0] - d[y][2];
-                    v[4 * y + 1] = d[y][1] + d[y][2];
-                    v[4 * y + 2] = d[y][2] - d[y][1];
-                    v[4 * y + 3] = d[y][1] - d[y][3];
-                }
+                for (int y = 0; y < 4; ++y) wino_bt4(d[y][0], d[y][1], d[y][2], d[y][3], v[4 * y], v[4 * y + 1], v[4 * y + 2], v[4 * y + 3]);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float4_t w4 = *reinterpret_cast<const float4_t*>(wl + (st * 4 + q) * 256);
@@ -461,19 +398,7 @@ __global__ __launch_bounds__(256, 2) void conv0_wino_kernel(WinoArgs a) {
         for (int oz = 0; oz < TZ; ++oz) {
             float row[2][8];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s0[4], s1[4];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const float m0 = acc[oz][b][r], m1 = acc[oz][4 + b][r], m2 = acc[oz][8 + b][r], m3 = acc[oz][12 + b][r];
-                    s0[b] = (m0 + m1) + m2;
-                    s1[b] = (m1 - m2) - m3;
-                }
-                row[0][2 * r] = (s0[0] + s0[1]) + s0[2];
-                row[0][2 * r + 1] = (s0[1] - s0[2]) - s0[3];
-                row[1][2 * r] = (s1[0] + s1[1]) + s1[2];
-                row[1][2 * r + 1] = (s1[1] - s1[2]) - s1[3];
-            }
+            for (int r = 0; r < 4; ++r) wino_out_xform(acc[oz], r, row[0] + 2 * r, row[1] + 2 * r);
             const int oz_g = cur.oz0 + oz;
 #pragma unroll
             for (int rr = 0; rr < 2; ++rr) {
@@ -481,14 +406,14 @@ __global__ __launch_bounds__(256, 2) void conv0_wino_kernel(WinoArgs a) {
                 const bool rok = oz_g < a.D && oy < a.H;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const int x = DMVS_WINO_TAU ? cur.ox0 + 16 * h + 4 * lk : cur.ox0 + 8 * lk + 4 * h;
+                    const int x = cur.ox0 + 8 * lk + 4 * h;
                     const unsigned pos = (unsigned)(co * out_vol + oz_g * out_plane + oy * a.W + x) * 4u;
                     v4u_t qv;
-                    qv.x = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 0] * sc + sh, lo));
-                    qv.y = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 1] * sc + sh, lo));
-                    qv.z = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 2] * sc + sh, lo));
-                    qv.w = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 3] * sc + sh, lo));
-                    __builtin_amdgcn_raw_buffer_store_b128(qv, rs_out, (rok && x < a.W && !((DMVS_WKO & 4) && qv.x != 0x12345678u)) ? pos : kInvalid, 0, 0);
+                    qv.x = wino_bn_relu(row[rr][4 * h + 0], sc, sh, lo);
+                    qv.y = wino_bn_relu(row[rr][4 * h + 1], sc, sh, lo);
+                    qv.z = wino_bn_relu(row[rr][4 * h + 2], sc, sh, lo);
+                    qv.w = wino_bn_relu(row[rr][4 * h + 3], sc, sh, lo);
+                    wino_store16<kNoStores>(rs_out, qv, (rok && x < a.W) ? pos : kInvalid);
                 }
             }
         }
@@ -519,17 +444,17 @@ __global__ __launch_bounds__(512, 2) void fpn_wino_kernel(WinoArgs a, const floa
     constexpr int WL_F = 3 * 4 * 256, WT_F = 8 * 3 * 256, W_F = WL_F + WT_F;
     constexpr int NI_LAT = (9 * PPP + 63) / 64, NI_TD = (32 * TD_PPP + 63) / 64, NI = NI_LAT + NI_TD;
     static_assert((8 * PPP) % 64 == 0, "the ones plane starts on an instruction boundary");
-    constexpr unsigned kInvalid = 0x80000000u;
+    constexpr unsigned kInvalid = kWinoInvalid;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // [W_F] filters, [2][STAGE_F]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // 0..7 = the tile row
     const int ln = lane & 15, lk = lane >> 4;
     struct Tile { int ox0, oy0, z; };
-    const int ntiles = a.nx * a.ny * a.nz, per_xcd = (ntiles + 7) >> 3;
+    const XcdTileWalk walk(a.nx * a.ny * a.nz);
     auto tile_of = [&](int vb, Tile& t) {
-        const int q = vb >> 3, id = (vb & 7) * per_xcd + q;
-        if (q >= per_xcd || id >= ntiles) return false;
+        int id;
+        if (!walk.id_of(vb, id)) return false;
         const int bx = id % a.nx, r = id / a.nx;
         t.ox0 = bx * 32; t.oy0 = (r % a.ny) * 16; t.z = r / a.ny;
         return true;
@@ -629,9 +554,7 @@ __global__ __launch_bounds__(512, 2) void fpn_wino_kernel(WinoArgs a, const floa
         auto read_lat = [&](int c, int b) {
             const float* p = lat_t + (c < 2 ? 4 * c + lk : 8) * PS + (2 * wave) * IXP + 2 + 2 * ln;
 #pragma unroll
-            for (int y = 0; y < 4; ++y)
-#pragma unroll
-                for (int h = 0; h < 3; ++h) lq[b][3 * y + h] = *reinterpret_cast<const float2_t*>(p + y * IXP + 2 * h);
+            for (int y = 0; y < 4; ++y) wino_read_pairs(p + y * IXP, lq[b] + 3 * y);
 #pragma unroll
             for (int q = 0; q < 4; ++q) lw[b][q] = *reinterpret_cast<const float4_t*>(wlat + (c * 4 + q) * 256);
         };
@@ -648,14 +571,11 @@ __global__ __launch_bounds__(512, 2) void fpn_wino_kernel(WinoArgs a, const floa
         auto comp_lat = [&](int b) {
             float d[4][4];
 #pragma unroll
-            for (int y = 0; y < 4; ++y) { d[y][0] = lq[b][3 * y].y; d[y][1] = lq[b][3 * y + 1].x; d[y][2] = lq[b][3 * y + 1].y; d[y][3] = lq[b][3 * y + 2].x; }
+            for (int y = 0; y < 4; ++y) wino_patch_row(lq[b] + 3 * y, d[y]);
 #pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const float t0 = d[0][x] - d[2][x], t1 = d[1][x] + d[2][x], t2 = d[2][x] - d[1][x], t3 = d[1][x] - d[3][x];
-                d[0][x] = t0; d[1][x] = t1; d[2][x] = t2; d[3][x] = t3;
-            }
+            for (int x = 0; x < 4; ++x) wino_bt4(d[0][x], d[1][x], d[2][x], d[3][x], d[0][x], d[1][x], d[2][x], d[3][x]);
 #pragma unroll
-            for (int y = 0; y < 4; ++y) {
+            for (int y = 0; y < 4; ++y) {   // (.) B, each value formed right in front of its MFMA (forming the four first reorders the MFMAs)
                 mma(4 * y + 0, d[y][0] - d[y][2], lw[b][y].x);
                 mma(4 * y + 1, d[y][1] + d[y][2], lw[b][y].y);
                 mma(4 * y + 2, d[y][2] - d[y][1], lw[b][y].z);
@@ -698,50 +618,26 @@ __global__ __launch_bounds__(512, 2) void fpn_wino_kernel(WinoArgs a, const floa
             const int hsel = co0 >= ch ? 1 : 0, cqi = (co0 - hsel * ch) >> 2;
             float y[4][2][2];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s0[4], s1[4];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const float m0 = acc[b][r], m1 = acc[4 + b][r], m2 = acc[8 + b][r], m3 = acc[12 + b][r];
-                    s0[b] = (m0 + m1) + m2;
-                    s1[b] = (m1 - m2) - m3;
-                }
-                y[r][0][0] = (s0[0] + s0[1]) + s0[2];
-                y[r][0][1] = (s0[1] - s0[2]) - s0[3];
-                y[r][1][0] = (s1[0] + s1[1]) + s1[2];
-                y[r][1][1] = (s1[1] - s1[2]) - s1[3];
-            }
+            for (int r = 0; r < 4; ++r) wino_out_xform(acc, r, y[r][0], y[r][1]);
 #pragma unroll
             for (int rr = 0; rr < 2; ++rr) {
                 const int oy = cur.oy0 + 2 * wave + rr;
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const int x = cur.ox0 + 2 * ln + e;
-                    v4u_t qv;
-                    qv.x = __builtin_bit_cast(unsigned, fmaxf(y[0][rr][e] * sc[0] + sh[0], lo));
-                    qv.y = __builtin_bit_cast(unsigned, fmaxf(y[1][rr][e] * sc[1 % NCO] + sh[1 % NCO], lo));
-                    qv.z = __builtin_bit_cast(unsigned, fmaxf(y[2][rr][e] * sc[2 % NCO] + sh[2 % NCO], lo));
-                    qv.w = __builtin_bit_cast(unsigned, fmaxf(y[3][rr][e] * sc[3 % NCO] + sh[3 % NCO], lo));
                     const unsigned off = (unsigned)(((hsel * a.D + oz_g) * cq + cqi) * plane + oy * a.W + x) * 16u;
-                    __builtin_amdgcn_raw_buffer_store_b128(qv, rs_out, (oy < a.H && x < a.W && !((DMVS_WKO & 4) && qv.x != 0x12345678u)) ? off : kInvalid, 0, 0);
+                    v4u_t qv;
+                    qv.x = wino_bn_relu(y[0][rr][e], sc[0], sh[0], lo);
+                    qv.y = wino_bn_relu(y[1][rr][e], sc[1], sh[1], lo);
+                    qv.z = wino_bn_relu(y[2][rr][e], sc[2], sh[2], lo);
+                    qv.w = wino_bn_relu(y[3][rr][e], sc[3], sh[3], lo);
+                    wino_store16<kNoStores>(rs_out, qv, (oy < a.H && x < a.W) ? off : kInvalid);
                 }
             }
         } else {
             float row[2][8];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s0[4], s1[4];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const float m0 = acc[b][r], m1 = acc[4 + b][r], m2 = acc[8 + b][r], m3 = acc[12 + b][r];
-                    s0[b] = (m0 + m1) + m2;
-                    s1[b] = (m1 - m2) - m3;
-                }
-                row[0][2 * r] = (s0[0] + s0[1]) + s0[2];
-                row[0][2 * r + 1] = (s0[1] - s0[2]) - s0[3];
-                row[1][2 * r] = (s1[0] + s1[1]) + s1[2];
-                row[1][2 * r + 1] = (s1[1] - s1[2]) - s1[3];
-            }
+            for (int r = 0; r < 4; ++r) wino_out_xform(acc, r, row[0] + 2 * r, row[1] + 2 * r);
             const int co = ln, x = cur.ox0 + 8 * lk;
 #pragma unroll
             for (int rr = 0; rr < 2; ++rr) {
@@ -750,11 +646,11 @@ __global__ __launch_bounds__(512, 2) void fpn_wino_kernel(WinoArgs a, const floa
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     v4u_t qv;
-                    qv.x = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 0] * sc[0] + sh[0], lo));
-                    qv.y = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 1] * sc[0] + sh[0], lo));
-                    qv.z = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 2] * sc[0] + sh[0], lo));
-                    qv.w = __builtin_bit_cast(unsigned, fmaxf(row[rr][4 * h + 3] * sc[0] + sh[0], lo));
-                    __builtin_amdgcn_raw_buffer_store_b128(qv, rs_out, (oy < a.H && x + 4 * h < a.W) ? pos + 16u * h : kInvalid, 0, 0);
+                    qv.x = wino_bn_relu(row[rr][4 * h + 0], sc[0], sh[0], lo);
+                    qv.y = wino_bn_relu(row[rr][4 * h + 1], sc[0], sh[0], lo);
+                    qv.z = wino_bn_relu(row[rr][4 * h + 2], sc[0], sh[0], lo);
+                    qv.w = wino_bn_relu(row[rr][4 * h + 3], sc[0], sh[0], lo);
+                    wino_store16<kNoStores>(rs_out, qv, (oy < a.H && x + 4 * h < a.W) ? pos + 16u * h : kInvalid);
                 }
             }
         }
@@ -771,25 +667,6 @@ long g_wino_stages = 0;
 long g_wino_persistent = 1;
 long g_wino_conv0_grid = 512;   // persistent workgroups of conv0_wino_kernel (dmvs_tune("wino_conv0_grid"), multiple of 8)
 namespace {
-
-struct WCfg { int cin, cout, kd, MB, GPC; };
-// the layers this kernel is compiled for; (MB = Cout / 16, GPC = 4-channel k-groups per chunk)
-const WCfg kWCfgs[] = {
-    {16, 16, 3, 1, 1},   // conv2   module.py:364
-    {32, 32, 3, 2, 1},   // conv4   module.py:367
-    {64, 64, 3, 4, 1},   // conv6   module.py:370
-    {64, 64, 1, 4, 1},   // refine conv6 (2D)  module.py:412
-    {16, 16, 1, 1, 2},   // FeatureNet conv1.1 / conv1.2
-    {32, 32, 1, 2, 2},   // FeatureNet conv2.1 / conv2.2 / out2
-    {2, 16, 3, 1, 0},    // conv0 of both branches fused (2 -> 8 + 8), (channel, depth tap) k-groups: conv0_wino_kernel
-    {32, 16, 1, 1, 1},   // FeatureNet out3 (alone; with the level-3 merge folded in: fpn_wino_kernel)
-};
-
-const WCfg* find_wcfg(int cin, int cout, int kd) {
-    for (const WCfg& c : kWCfgs)
-        if (c.cin == cin && c.cout == cout && c.kd == kd) return &c;
-    return nullptr;
-}
 
 template <int KD, int MB, int MBW, int TZ, int TRW, int GPC, bool Q4 = false>
 int launch_wino(WinoArgs a, bool single_buf, hipStream_t st) {
@@ -809,7 +686,7 @@ int launch_wino(WinoArgs a, bool single_buf, hipStream_t st) {
     DMVS_LAUNCH_CHECK();
 }
 
-int launch_conv0_wino(WinoArgs a, hipStream_t st) {
+int launch_conv0_wino(WinoArgs a, bool, hipStream_t st) {
     constexpr int PS0 = 4 * 10 * 40, PS = PS0 + (32 - PS0 % 64 + 64) % 64;
     constexpr size_t lds = (2 * 4 * 256 + 2 * (size_t)((2 * PS + 63) & ~63)) * sizeof(float);
     a.nx = ceil_div(a.W, 32); a.ny = ceil_div(a.H, 8); a.nz = ceil_div(a.D, 2);
@@ -819,37 +696,48 @@ int launch_conv0_wino(WinoArgs a, hipStream_t st) {
     DMVS_LAUNCH_CHECK();
 }
 
-// output rows / planes of a workgroup of the variant dispatch() picks (one source of truth for dmvs_conv3d_wino_plan)
-void wino_tile(int Cout, int kdepth, int D, int& tz, int& ty) {
-    const bool flat = kdepth == 1 || D == 1;
-    tz = (kdepth == 3 && Cout == 16 && !flat) ? 2 : 1;   // (conv0: 2 planes x 8 rows whatever the depth)
-    ty = Cout == 64 ? 4 : (Cout == 16 && flat) ? 16 : 8;
+// The compiled variants, each described ONCE: dispatch, dmvs_conv3d_wino_plan, dmvs_conv3d_wino_weight_floats and the packer
+// read a row and nothing else.
+typedef int (*WinoLaunch)(WinoArgs, bool single_buf, hipStream_t);
+struct WCfg {
+    int cin, cout, kd;
+    bool flat;              // serves depth-1 volumes only (listed in front of the general row of its shape)
+    int MB, GPC;            // 16-channel output blocks; 4-channel k-groups per chunk (0: conv0's (channel, depth tap) pairs)
+    int TZ, TY;             // output planes / rows of a workgroup
+    bool single_buf;        // prefers one LDS stage
+    WinoLaunch launch[2];   // planar / DMVS_OUT_Q4 output; nullptr = not compiled
+    long ksteps() const { return GPC ? (long)cin / 4 * kd : 2; }   // MFMA k-steps of 4 over the whole filter
+};
+template <int KD, int MB, int MBW, int TZ, int TRW, int GPC>
+constexpr WCfg wino_row(int cin, int cout, bool flat, bool single_buf) {
+    return {cin, cout, KD, flat, MB, GPC, TZ, WinoGeom<KD, MB, MBW, TZ, TRW, GPC>::TY, single_buf,
+            {launch_wino<KD, MB, MBW, TZ, TRW, GPC, false>, launch_wino<KD, MB, MBW, TZ, TRW, GPC, true>}};
 }
+const WCfg kWCfgs[] = {
+    wino_row<3, 1, 1, 1, 2, 1>(16, 16, true, true),     // conv2 on a depth-1 volume (refine passes)
+    wino_row<3, 1, 1, 2, 1, 1>(16, 16, false, true),    // conv2   module.py:364
+    wino_row<3, 2, 2, 1, 1, 1>(32, 32, false, true),    // conv4   module.py:367
+    wino_row<3, 4, 2, 1, 1, 1>(64, 64, false, true),    // conv6   module.py:370
+    wino_row<1, 4, 2, 1, 1, 1>(64, 64, false, true),    // refine conv6 (2D)  module.py:412
+    wino_row<1, 1, 1, 1, 2, 2>(16, 16, false, false),   // FeatureNet conv1.1 / conv1.2
+    wino_row<1, 2, 2, 1, 1, 2>(32, 32, false, false),   // FeatureNet conv2.1 / conv2.2 / out2
+    // conv0 of both branches fused (2 -> 8 + 8), (channel, depth tap) k-groups: conv0_wino_kernel, 2 planes x 8 rows, planar only
+    {2, 16, 3, false, 1, 0, 2, 8, false, {launch_conv0_wino, nullptr}},
+    wino_row<1, 1, 1, 1, 2, 1>(32, 16, false, false),   // FeatureNet out3 (alone; with the level-3 merge folded in: fpn_wino_kernel)
+};
 
-template <bool Q4>
-int dispatch(const WinoArgs& a, int kdepth, hipStream_t st) {
-    const int Cout = a.Cout;
-    const bool flat = kdepth == 1 || a.D == 1;
-    if (kdepth == 3) {
-        if (a.Cin == 2 && Cout == 16) return Q4 ? DMVS_EUNSUPPORTED : launch_conv0_wino(a, st);
-        if (a.Cin == 16 && Cout == 16) return flat ? launch_wino<3, 1, 1, 1, 2, 1, Q4>(a, true, st) : launch_wino<3, 1, 1, 2, 1, 1, Q4>(a, true, st);
-        if (a.Cin == 32 && Cout == 32) return launch_wino<3, 2, 2, 1, 1, 1, Q4>(a, true, st);
-        if (a.Cin == 64 && Cout == 64) return launch_wino<3, 4, 2, 1, 1, 1, Q4>(a, true, st);
-    } else {
-        if (a.Cin == 16 && Cout == 16) return launch_wino<1, 1, 1, 1, 2, 2, Q4>(a, false, st);
-        if (a.Cin == 32 && Cout == 32) return launch_wino<1, 2, 2, 1, 1, 2, Q4>(a, false, st);
-        if (a.Cin == 64 && Cout == 64) return launch_wino<1, 4, 2, 1, 1, 1, Q4>(a, true, st);
-        if (a.Cin == 32 && Cout == 16) return launch_wino<1, 1, 1, 1, 2, 1, Q4>(a, false, st);
-    }
-    return DMVS_EUNSUPPORTED;
+// D = 0: any depth (the filter layout does not depend on it)
+const WCfg* find_wcfg(int cin, int cout, int kd, int D = 0) {
+    for (const WCfg& c : kWCfgs)
+        if (c.cin == cin && c.cout == cout && c.kd == kd && (!c.flat || D == 1)) return &c;
+    return nullptr;
 }
 
 }  // namespace
 
 extern "C" long dmvs_conv3d_wino_weight_floats(int Cin, int Cout, int kdepth) {
     const WCfg* c = find_wcfg(Cin, Cout, kdepth);
-    if (c && Cin == 2) return 2 * 4 * 256;
-    return c ? (long)Cin / 4 * kdepth * c->MB * 16 * 64 : 0;
+    return c ? c->ksteps() * c->MB * 4 * 256 : 0;   // per k-step and 16-channel block: 16 transform positions x 64 lanes
 }
 
 extern "C" int dmvs_pack_conv_weights_wino(const float* w, float* out, int Cin, int Cout, int kdepth) {
@@ -858,7 +746,7 @@ extern "C" int dmvs_pack_conv_weights_wino(const float* w, float* out, int Cin, 
     const int NT = 9 * kdepth, cich = 4 * c->GPC;
     size_t n = 0;
     double g[9];
-    if (Cin == 2) {   // conv0_wino_kernel: k-step, quarter, lane (cout = l % 16, channel = (l / 16) & 1, depth selector l / 32), xi % 4
+    if (c->GPC == 0) {   // conv0_wino_kernel: k-step, quarter, lane (cout = l % 16, channel = (l / 16) & 1, depth selector l / 32), xi % 4
         for (int st = 0; st < 2; ++st)
             for (int q = 0; q < 4; ++q)
                 for (int l = 0; l < 64; ++l)
@@ -868,7 +756,7 @@ extern "C" int dmvs_pack_conv_weights_wino(const float* w, float* out, int Cin, 
                         for (int t = 0; t < 9; ++t) g[t] = w[((size_t)co * Cin + ci) * NT + kz * 9 + t];
                         out[n++] = (st == 1 && zsel == 1) ? 0.f : (float)wino_filter(g, ya, xb);
                     }
-        return n == 2048 ? 0 : DMVS_EINVAL;
+        return n == (size_t)dmvs_conv3d_wino_weight_floats(Cin, Cout, kdepth) ? 0 : DMVS_EINVAL;
     }
     // order: chunk, kz, k-group, 16-channel block, quarter q of the 16 transform positions, lane, xi % 4
     for (int ci0 = 0; ci0 < Cin; ci0 += cich)
@@ -887,11 +775,9 @@ extern "C" int dmvs_pack_conv_weights_wino(const float* w, float* out, int Cin, 
 }
 
 extern "C" int dmvs_conv3d_wino_plan(int Cin, int Cout, int D, int H, int W, int kdepth) {
-    if (!find_wcfg(Cin, Cout, kdepth) || D < 1 || H < 1 || W < 1 || W % 4 != 0) return DMVS_EUNSUPPORTED;
-    int tz, ty;
-    wino_tile(Cout, kdepth, D, tz, ty);
-    if (Cin == 2) { tz = 2; ty = 8; }
-    const long n = (long)ceil_div(W, 32) * ceil_div(H, ty) * ceil_div(D, tz);
+    const WCfg* c = find_wcfg(Cin, Cout, kdepth, D);
+    if (!c || D < 1 || H < 1 || W < 1 || W % 4 != 0) return DMVS_EUNSUPPORTED;
+    const long n = (long)ceil_div(W, 32) * ceil_div(H, c->TY) * ceil_div(D, c->TZ);
     return n > 0x3fffffff ? 0x3fffffff : (int)n;
 }
 
@@ -900,14 +786,15 @@ extern "C" int dmvs_conv3d_wino(const float* in, float* out, const float* w_pack
     if (!in || !out || !w_packed || D < 1 || H < 1 || W < 1) return DMVS_EINVAL;
     if ((scale == nullptr) != (shift == nullptr)) return DMVS_EINVAL;
     if (flags & ~(DMVS_RELU | DMVS_OUT_Q4)) return DMVS_EUNSUPPORTED;   // no residual
-    const WCfg* c = find_wcfg(Cin, Cout, kdepth);
-    if (!c) return DMVS_EUNSUPPORTED;
+    const WCfg* c = find_wcfg(Cin, Cout, kdepth, D);
+    const WinoLaunch launch = c ? c->launch[(flags & DMVS_OUT_Q4) ? 1 : 0] : nullptr;
+    if (!launch) return DMVS_EUNSUPPORTED;
     if (W % 4 != 0 || ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) != 0) return DMVS_EUNSUPPORTED;
     if ((long)std::max(2, 4 * c->GPC) * D * H * W >= (1L << 28) || (long)Cout * D * H * W >= (1L << 29)) return DMVS_EINVAL;
     WinoArgs a = {};
     a.in = in; a.out = out; a.w = w_packed; a.scale = scale; a.shift = shift;
     a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.relu = (flags & DMVS_RELU) ? 1 : 0;
-    return (flags & DMVS_OUT_Q4) ? dispatch<true>(a, kdepth, (hipStream_t)stream) : dispatch<false>(a, kdepth, (hipStream_t)stream);
+    return launch(a, c->single_buf, (hipStream_t)stream);
 }
 
 // filters of fpn_wino_kernel: [3 lateral k-groups][4 quarters][64 lanes][4] then [8 top-down k-groups][3 quarters][64 lanes][4]

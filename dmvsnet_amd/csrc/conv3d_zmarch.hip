@@ -33,6 +33,7 @@
 // Needs W % 4 == 0 and 16-byte aligned tensors (as K3w); otherwise DMVS_EUNSUPPORTED and the caller runs K3w / K3.
 #include "common.h"
 #include "tile_loader.h"
+#include "wino.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -49,8 +50,6 @@ long g_k3z_zs = 0;
 
 namespace {
 
-typedef float acc4_t __attribute__((ext_vector_type(4)));
-typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
 #if DMVS_ZKO & 4
 __device__ __forceinline__ acc4_t z_mfma(float a, float b, acc4_t c) { c.x += a; c.y += b; return c; }   // keeps the operands alive
 #else
@@ -86,7 +85,8 @@ template <int RING>
 __global__ __launch_bounds__(256, ZGeom<RING>::WPS) void zmarch_kernel(ZArgs a) {
     typedef ZGeom<RING> G;
     constexpr int IXP = G::IXP, PS = G::PS, NS = G::NS;
-    constexpr unsigned kInvalid = 0x80000000u;
+    constexpr unsigned kInvalid = kWinoInvalid;
+    typedef ByteRange<2> YX;   // the loader's range test of a piece's (row, x)
     extern __shared__ __attribute__((aligned(16))) float smem[];   // [RING][STAGE_F] planes, [TRASH_F], [2][EX1_F] exchange
     float* const ex = smem + RING * G::STAGE_F + G::TRASH_F;
 
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256, ZGeom<RING>::WPS) void zmarch_kernel(ZArgs a) 
         const bool okp = qi < G::NI && rem < G::PLANE;
         const int row = rem / IXP, x = rem - row * IXP;
         roff[sl] = c * vol + row * a.W + x;
-        yx[sl] = okp ? (unsigned)(row | (x << 8)) : 0x3f3fu;   // a pad piece fails every range test below
+        yx[sl] = okp ? YX::pack(row, x) : YX::kNever;   // a pad piece fails every range test below
     }
     // the issue stream runs RING - 1 stages ahead of the compute stream: its own (column, plane) counters and the lane's byte
     // offsets of the column it is in
@@ -174,17 +174,14 @@ __global__ __launch_bounds__(256, ZGeom<RING>::WPS) void zmarch_kernel(ZArgs a) 
             coords(pq, ox0, oy0, qz0, qzse);
             qnt = qzse + 2;
             const int yb = oy0 - 1, xb = ox0 - 4;
-            // valid tile rows / columns of this column, [lo, hi] (uniform); the lane's (y, x) bytes are range-checked together:
-            // with the guard bit 7 set, a byte-wise subtraction keeps the guard iff it did not borrow (K3r's test)
+            // valid tile rows / columns of this column, [lo, hi] (uniform); the lane's (y, x) bytes are range-checked together
             const unsigned yl = max(0, -yb), xl = max(0, -xb);
             const unsigned yh = min(G::IY, a.H - yb) - 1, xh = min(IXP, a.W - xb) - 1;
-            const unsigned LO = yl | (xl << 8), HG = (yh | (xh << 8)) | 0x8080u;
+            const unsigned LO = YX::pack(yl, xl), HG = YX::pack_hi(yh, xh);
             const int base = yb * a.W + xb;
 #pragma unroll
             for (int sl = 0; sl < NS; ++sl) {
-                const unsigned ge = (yx[sl] | 0x8080u) - LO, le = HG - yx[sl];
-                const bool ok = (ge & le & 0x8080u) == 0x8080u;
-                voff[sl] = ok ? (unsigned)(roff[sl] + base) * 4u : kInvalid;
+                voff[sl] = YX::in_range(yx[sl], LO, HG) ? (unsigned)(roff[sl] + base) * 4u : kInvalid;
             }
         }
         const int pz = qz0 - 1 + tq;
@@ -209,7 +206,7 @@ __global__ __launch_bounds__(256, ZGeom<RING>::WPS) void zmarch_kernel(ZArgs a) 
         if (!(DMVS_ZKO & 1)) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(smem + dsto), 16, vo, so, 0, 0);
     };
 
-    // ---- patch reads (K3r's layout): the lane's tile (tx, ty), channel lk of a k-group; row i of B^T d = d[ra] + sg * d[rb]
+    // ---- patch reads (K3r's layout): the lane's tile (tx, ty), channel lk of a k-group; the wave's row of B^T d (wino.h)
     const int ti = wave;
     const int ra = ti == 0 ? 0 : (ti == 2 ? 2 : 1), rb = ti == 0 ? 2 : (ti == 1 ? 2 : (ti == 2 ? 1 : 3));
     const float sg = ti == 1 ? 1.f : -1.f;
@@ -232,21 +229,21 @@ __global__ __launch_bounds__(256, ZGeom<RING>::WPS) void zmarch_kernel(ZArgs a) 
 #pragma unroll
         for (int rs = 0; rs < 2; ++rs) {
             if (frr == 0) {
-                y[2 * rs] = (P[0][rs].x + P[1][rs].x) + P[2][rs].x;
-                y[2 * rs + 1] = (P[0][rs].y + P[1][rs].y) + P[2][rs].y;
+                y[2 * rs] = wino_at0(P[0][rs].x, P[1][rs].x, P[2][rs].x);
+                y[2 * rs + 1] = wino_at0(P[0][rs].y, P[1][rs].y, P[2][rs].y);
             } else {
-                y[2 * rs] = (P[1][rs].x - P[2][rs].x) - P[3][rs].x;
-                y[2 * rs + 1] = (P[1][rs].y - P[2][rs].y) - P[3][rs].y;
+                y[2 * rs] = wino_at1(P[1][rs].x, P[2][rs].x, P[3][rs].x);
+                y[2 * rs + 1] = wino_at1(P[1][rs].y, P[2][rs].y, P[3][rs].y);
             }
         }
         const int x = ox0 + 4 * fxh, yy = oy0 + 2 * lk + frr;
         const unsigned pos = (unsigned)(ln * vol + oz * plane + yy * a.W + x) * 4u;
-        v4u_t qv;
-        qv.x = __builtin_bit_cast(unsigned, fmaxf(y[0] * bsc + bsh, lo));
-        qv.y = __builtin_bit_cast(unsigned, fmaxf(y[1] * bsc + bsh, lo));
-        qv.z = __builtin_bit_cast(unsigned, fmaxf(y[2] * bsc + bsh, lo));
-        qv.w = __builtin_bit_cast(unsigned, fmaxf(y[3] * bsc + bsh, lo));
-        __builtin_amdgcn_raw_buffer_store_b128(qv, rs_out, (yy < a.H && x < a.W && !((DMVS_ZKO & 2) && qv.x != 0x12345678u)) ? pos : kInvalid, 0, 0);
+        v4u_t qv;   // (element by element: handing y to store_planar_bn_relu as an array costs this kernel registers)
+        qv.x = wino_bn_relu(y[0], bsc, bsh, lo);
+        qv.y = wino_bn_relu(y[1], bsc, bsh, lo);
+        qv.z = wino_bn_relu(y[2], bsc, bsh, lo);
+        qv.w = wino_bn_relu(y[3], bsc, bsh, lo);
+        wino_store16<(DMVS_ZKO & 2) != 0>(rs_out, qv, (yy < a.H && x < a.W) ? pos : kInvalid);
     };
 
     // ---- pipeline.  Knock-outs of the first build (barrier at the top of a stage: patch reads -> transform -> 48 MFMAs -> exchange;
@@ -274,21 +271,13 @@ __global__ __launch_bounds__(256, ZGeom<RING>::WPS) void zmarch_kernel(ZArgs a) 
 #pragma unroll
         for (int kg = 0; kg < 4; ++kg) {
             const int o = kg * 4 * PS;
-            rd[kg][0] = *reinterpret_cast<const float2_t*>(pa + o);
-            rd[kg][1] = *reinterpret_cast<const float2_t*>(pa + o + 2);
-            rd[kg][2] = *reinterpret_cast<const float2_t*>(pa + o + 4);
-            rd[kg][3] = *reinterpret_cast<const float2_t*>(pb + o);
-            rd[kg][4] = *reinterpret_cast<const float2_t*>(pb + o + 2);
-            rd[kg][5] = *reinterpret_cast<const float2_t*>(pb + o + 4);
+            wino_read_pairs(pa + o, rd[kg]);
+            wino_read_pairs(pb + o, rd[kg] + 3);
         }
     };
     auto patch_xform = [&](float (&vo)[4][4]) {
 #pragma unroll
-        for (int kg = 0; kg < 4; ++kg) {
-            const float t0 = fmaf(sg, rd[kg][3].y, rd[kg][0].y), t1 = fmaf(sg, rd[kg][4].x, rd[kg][1].x),
-                        t2 = fmaf(sg, rd[kg][4].y, rd[kg][1].y), t3 = fmaf(sg, rd[kg][5].x, rd[kg][2].x);
-            vo[kg][0] = t0 - t2; vo[kg][1] = t1 + t2; vo[kg][2] = t2 - t1; vo[kg][3] = t1 - t3;
-        }
+        for (int kg = 0; kg < 4; ++kg) wino_in_row(sg, rd[kg], vo[kg]);
     };
     // prologue: the first plane, alone; then the second one flies while the first is read and transformed
     issue_begin();
@@ -336,13 +325,7 @@ __global__ __launch_bounds__(256, ZGeom<RING>::WPS) void zmarch_kernel(ZArgs a) 
             // tile (tx = r, ty = lk) of channel ln), handed to the finishing waves through LDS
             float2_t* const exw = reinterpret_cast<float2_t*>(ex + (k & 1) * G::EX1_F) + (size_t)wave * 4 * 64 + lane;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float m0 = done[0][r], m1 = done[1][r], m2 = done[2][r], m3 = done[3][r];
-                float2_t sv;
-                sv.x = (m0 + m1) + m2;
-                sv.y = (m1 - m2) - m3;
-                exw[r * 64] = sv;
-            }
+            for (int r = 0; r < 4; ++r) exw[r * 64] = wino_out_half(done[0][r], done[1][r], done[2][r], done[3][r]);
         }
         // ---- C
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
