@@ -9,5 +9,8 @@ from .mvsnet import CostAgg, CostRegNet, DepthNet, FeatureNet, MVSNet, ViewFeatu
 
 from . import eval_io  # noqa: F401  (PFM / cam I/O, eval dataset, Model.test step 1)
 from . import fusion   # noqa: F401  (geometric-consistency fusion filter, PLY)
+from . import cloud_eval  # noqa: F401  (DTU accuracy / completeness of a fused cloud)
+from .cloud_eval import evaluate_dtu, max_dist_cp, point_compare, reduce_points, scan_stats  # noqa: F401
 
-__all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFeatures", "shard_source_views", "eval_io", "fusion"]
+__all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFeatures", "shard_source_views", "eval_io", "fusion",
+           "cloud_eval", "reduce_points", "max_dist_cp", "point_compare", "scan_stats", "evaluate_dtu"]

@@ -20,6 +20,7 @@ ABI_VERSION = 140   # include/dmvs.h DMVS_VERSION
 _p = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
+_d = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/dmvs.h one to one.
 SIGNATURES = {
@@ -70,6 +71,13 @@ SIGNATURES = {
     "dmvs_fuse_workgroups": (ctypes.c_long, [_i, _i]),
     "dmvs_fuse_view": (_i, [_p, _p, _p, _p, _i, _i, _i, ctypes.POINTER(_p), _p, _f, _f, _f, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
     "dmvs_fuse_emit": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "dmvs_cloud_cell_keys": (_i, [_p, _i, _p, _d, _p, _p, _p]),
+    "dmvs_cloud_cell_runs": (_i, [_p, _p, _i, _p, _p, _p]),
+    "dmvs_cloud_thin_round": (_i, [_p, _p, _p, _p, _p, _p, _i, _d, _p, _p]),
+    "dmvs_cloud_nn": (_i, [_p, _p, _p, _i, _p, _d, _p, _p, _p, _i, _i, _d, _p, _p, _p, _p, _p, _p]),
+    "dmvs_cloud_in_mask": (_i, [_p, _i, _p, _d, _p, _p, _p, _p]),
+    "dmvs_cloud_above_plane": (_i, [_p, _i, _p, _p, _p]),
+    "dmvs_cloud_in_box": (_i, [_p, _i, _p, _p, _p, _p]),
     "dmvs_prob_regress": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p]),
     "dmvs_depth_select": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "dmvs_depth_regress": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

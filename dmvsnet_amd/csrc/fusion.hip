@@ -308,3 +308,6 @@ extern "C" int dmvs_fuse_emit(const unsigned char* masks, const double* depth_av
     fuse_emit_kernel<<<nblk, FUSE_WG, 0, (hipStream_t)stream>>>(a);
     DMVS_LAUNCH_CHECK();
 }
+
+// N5: the point-cloud evaluation kernels (an extension of N4: what becomes of the fused cloud) live in a header of their own
+#include "cloud_eval.h"

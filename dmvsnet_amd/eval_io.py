@@ -322,6 +322,12 @@ def save_depth_maps(network, datapath: str, testlist: Sequence[str], outdir: str
     return written
 
 
+def ply_path(outdir: str, scan: str, pcd_dir: str = "pcd") -> str:
+    """Where run_test writes a scan's fused cloud: DTU scans under the name the DTU evaluation reads (mvsnetNNN_l3.ply)."""
+    name = "mvsnet{:0>3}_l3.ply".format(int(scan[4:])) if scan.startswith("scan") and scan[4:].isdigit() else "{}.ply".format(scan)
+    return os.path.join(outdir, pcd_dir, name)
+
+
 @torch.no_grad()
 def run_test(network, datapath: str, testlist: Sequence[str], outdir: str, num_view: int, max_h: int, max_w: int,
              numdepth: int = 192, interval_scale: float = 1.06, inverse_depth: bool = False, conf=(0.1, 0.15, 0.7),
@@ -344,10 +350,6 @@ def run_test(network, datapath: str, testlist: Sequence[str], outdir: str, num_v
     Returns the mask statistics of the last reference view per scene."""
     from . import fusion
 
-    def ply_path(scan):
-        name = "mvsnet{:0>3}_l3.ply".format(int(scan[4:])) if scan.startswith("scan") and scan[4:].isdigit() else "{}.ply".format(scan)
-        return os.path.join(outdir, "pcd", name)
-
     def fusion_args(scan):
         sc = (scene_cfg or {}).get(scan, {})
         return (fusion.read_pair_file(os.path.join(datapath, scan, "pair.txt")),
@@ -367,7 +369,7 @@ def run_test(network, datapath: str, testlist: Sequence[str], outdir: str, num_v
             return fusion.ScanFusion(pairs, **kw)
 
         def end(scan, fz):
-            out[scan] = fz.write(os.path.join(outdir, scan), ply_path(scan))
+            out[scan] = fz.write(os.path.join(outdir, scan), ply_path(outdir, scan))
 
         scan_mod.save_depth_maps_cached(network, datapath, testlist, outdir, num_view, max_h, max_w, numdepth,
                                         interval_scale, inverse_depth, device, True, fix_res, scene_cfg,
@@ -380,5 +382,5 @@ def run_test(network, datapath: str, testlist: Sequence[str], outdir: str, num_v
     stats = {}
     for scan in testlist:
         pairs, kw = fusion_args(scan)
-        stats[scan] = fusion.fuse_scene(pairs, os.path.join(outdir, scan), ply_path(scan), **kw)
+        stats[scan] = fusion.fuse_scene(pairs, os.path.join(outdir, scan), ply_path(outdir, scan), **kw)
     return stats

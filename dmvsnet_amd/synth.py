@@ -22,6 +22,7 @@ import torch
 
 __all__ = [
     "synth_fusion_scene",
+    "synth_cloud_scene",
     "synth_images",
     "synth_cameras",
     "synth_depth_values",
@@ -181,3 +182,66 @@ def synth_fusion_scene(H: int, W: int, V: int, seed: int = 0, z0: float = 620.0)
         confs.append(g.random((3, H, W), dtype=np.float32))
         imgs.append(g.random((H, W, 3), dtype=np.float32))
     return cams, depths, confs, imgs
+
+
+def _cloud_surface(x, y, L):
+    """The smooth height field of synth_cloud_scene (mm); slopes stay below ~0.5."""
+    return 0.04 * L * np.sin(3.0 * np.pi * x / L) * np.cos(2.0 * np.pi * y / L) + 0.02 * L * np.cos(5.0 * x / L + 1.0)
+
+
+def synth_cloud_scene(seed: int, n_data: int, n_stl: int, noise: float = 0.12, outlier_share: float = 0.03,
+                      outside_share: float = 0.01, mask_cells: int = 64) -> Dict[str, np.ndarray]:
+    """A deterministic DTU-evaluation scene (millimetres) for cloud_eval's tests and benchmark: one smooth surface sampled twice.
+
+    ``stl``  [~n_stl,3] float32: a jittered 0.3 mm lattice on the surface -- no two points closer than 0.2 mm, as the dataset's
+             reference clouds are thinned; the surface dips below the plane ``P`` in places.
+    ``data`` [n_data,3] float32: random samples with a density that varies in patches (denser than 0.2 mm where it is high),
+             discs without data (holes), Gaussian noise along z, a share of far outliers (5 .. 90 mm off the surface, some
+             beyond 60 mm of anything), and a share of points outside ``BB``.
+    ``ObsMask`` uint8 [nx,ny,nz] / ``BB`` [2,3] / ``Res``: the observability volume (a band around the surface, minus a border
+             strip), its bounding box (not a multiple of 60 mm) and voxel size; ``P`` [4]: the ground plane."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    side = max(int(round(np.sqrt(max(n_stl, 1)))), 2)
+    step = 0.3
+    L = side * step
+    gx, gy = np.meshgrid(np.arange(side, dtype=np.float64), np.arange(side, dtype=np.float64), indexing="ij")
+    sx = (gx.ravel() + 0.5) * step + rng.uniform(-0.04, 0.04, side * side)
+    sy = (gy.ravel() + 0.5) * step + rng.uniform(-0.04, 0.04, side * side)
+    stl = np.stack([sx, sy, _cloud_surface(sx, sy, L)], 1).astype(np.float32)
+
+    # data: rejection-sample (x, y) against a patchy density, drop the holes, keep the first n_data
+    holes = rng.uniform(0.1 * L, 0.9 * L, (6, 2))
+    hole_r = rng.uniform(0.03 * L, 0.07 * L, 6)
+    parts, have = [], 0
+    while have < n_data:
+        m = int(1.6 * (n_data - have)) + 64
+        x, y = rng.uniform(0, L, m), rng.uniform(0, L, m)
+        dens = 0.55 + 0.45 * np.sin(7.0 * x / L + 0.3) * np.sin(5.0 * y / L + 1.1)
+        keep = rng.uniform(0, 1, m) < dens
+        for (hx, hy), hr in zip(holes, hole_r):
+            keep &= (x - hx) ** 2 + (y - hy) ** 2 > hr * hr
+        parts.append(np.stack([x[keep], y[keep]], 1))
+        have += int(keep.sum())
+    xy = np.concatenate(parts)[:n_data]
+    z = _cloud_surface(xy[:, 0], xy[:, 1], L) + rng.normal(0.0, noise, n_data)
+    kind = rng.uniform(0, 1, n_data)
+    out = kind < outlier_share
+    z = np.where(out, z + rng.choice([-1.0, 1.0], n_data) * rng.uniform(5.0, 90.0, n_data), z)
+    data = np.stack([xy[:, 0], xy[:, 1], z], 1)
+    far = (kind >= outlier_share) & (kind < outlier_share + outside_share)
+    data[far, 0] += rng.choice([-1.0, 1.0], n_data)[far] * (L + rng.uniform(20.0, 150.0, n_data)[far])
+    data = data.astype(np.float32)
+
+    zr = 0.07 * L
+    bb = np.array([[-7.0, -11.0, -zr - 35.0], [L + 9.0, L + 5.0, zr + 41.0]], dtype=np.float64)
+    res = float((bb[1] - bb[0]).max() / mask_cells)
+    dims = np.floor((bb[1] - bb[0]) / res).astype(np.int64) + 1
+    cx = bb[0, 0] + np.arange(dims[0]) * res
+    cy = bb[0, 1] + np.arange(dims[1]) * res
+    cz = bb[0, 2] + np.arange(dims[2]) * res
+    X, Y, Z = np.meshgrid(cx, cy, cz, indexing="ij")
+    band = np.abs(Z - _cloud_surface(np.clip(X, 0, L), np.clip(Y, 0, L), L)) < 10.0 + res
+    inner = (X > 0.05 * L) & (X < L + 2.0) & (Y > -2.0) & (Y < 0.93 * L)
+    obs = np.ascontiguousarray(band & inner, dtype=np.uint8)
+    plane = np.array([0.02, -0.015, 1.0, 0.012 * L], dtype=np.float64)
+    return dict(data=data, stl=stl, ObsMask=obs, BB=bb, Res=res, P=plane)

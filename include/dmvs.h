@@ -25,7 +25,7 @@ extern "C" {
 
 typedef void* dmvs_stream_t; /* hipStream_t */
 
-#define DMVS_VERSION 140 /* 0.1.4 (r06): + dmvs_prob_regress / dmvs_depth_select (`prob` -> K4); 0.1.3 (r06): + K3z dmvs_conv3d_zmarch / _weight_floats / dmvs_pack_conv_weights_zmarch, + the bf16-split probe dmvs_conv3d_split_probe / _weight_floats / dmvs_pack_conv_weights_split; 0.1.2 (r05): + K3r dmvs_conv3d_coarse / _weight_floats / dmvs_pack_conv_weights_coarse; 0.1.1: DMVS_OUT_Q4 moved to bit 3 (value 8); bit 2 (value 4, r02's DMVS_OUT_HWC2: two
+#define DMVS_VERSION 140 /* 0.1.4: + N5 dmvs_cloud_cell_keys / _cell_runs / _thin_round / _nn / _in_mask / _above_plane / _in_box (additive, same version); 0.1.4 (r06): + dmvs_prob_regress / dmvs_depth_select (`prob` -> K4); 0.1.3 (r06): + K3z dmvs_conv3d_zmarch / _weight_floats / dmvs_pack_conv_weights_zmarch, + the bf16-split probe dmvs_conv3d_split_probe / _weight_floats / dmvs_pack_conv_weights_split; 0.1.2 (r05): + K3r dmvs_conv3d_coarse / _weight_floats / dmvs_pack_conv_weights_coarse; 0.1.1: DMVS_OUT_Q4 moved to bit 3 (value 8); bit 2 (value 4, r02's DMVS_OUT_HWC2: two
                             PIXEL-MAJOR halves) is retired and rejected with DMVS_EUNSUPPORTED -- a caller built against
                             version 100 can no longer get the quad-planar layout silently; dmvs_tune("k1_variant") is
                             gone (the launch variant is an argument of dmvs_warp_corr_q4) */
@@ -390,6 +390,45 @@ int dmvs_fuse_view(const float* depth_ref, const float* conf3, const float* conf
                    double* depth_avg64, int* counts, dmvs_stream_t stream);
 int dmvs_fuse_emit(const unsigned char* masks, const double* depth_avg64, const int* counts, int H, int W,
                    const double* kinv9, const double* einv16, int* offsets, float* xyz, dmvs_stream_t stream);
+
+/* N5: DTU point-cloud evaluation (csrc/cloud_eval.h, host side dmvsnet_amd/cloud_eval.py) -- accuracy / completeness of a fused
+ * cloud against the scanned reference cloud; replaces the arithmetic of scripts/evaluation_dtu/*.m.  Clouds are [n][3] fp32;
+ * every difference and distance is fp64 (dx*dx + dy*dy + dz*dz in that order, unfused, compared squared, one sqrt at the end).
+ * origin3 / dims3 / bb0 / lo3 / hi3 / plane4 / mask_dims3 are HOST arrays.
+ *
+ * dmvs_cloud_cell_keys: keys [n] i64 = (iz * ny + iy) * nx + ix of the cell floor((p - origin) / cell) per axis (x fastest), or
+ *   INT64_MAX outside the grid.  DMVS_EINVAL when an axis has more than 2^21 cells.  The caller sorts the cloud by key; its
+ *   occupied cells are the sorted unique keys ukeys [M] with ustart [M + 1] i32 the first point of each.
+ * dmvs_cloud_cell_runs: runs [M][9][2] i32 = the point ranges [begin, end) of the nine x-runs of every occupied cell's 27-cell
+ *   neighbourhood (the candidates of rangesearch, reducePts_haa.m:21; one binary search per run and cell).
+ * dmvs_cloud_thin_round: one sweep of the thinning loop reducePts_haa.m:23-29 written as a fixed-point iteration with the same
+ *   result.  state [n] u8: 0 undecided / 1 kept / 2 removed; prio [n] i32 = position in the visit order (RandOrd,
+ *   reducePts_haa.m:9); cell_of [n] i32 = occupied cell of each (key-sorted) point; todo [n_todo] i32 the points to visit, or
+ *   NULL: all of 0 .. n_todo - 1.  An undecided point is removed when an earlier neighbour (distance <= dst) is kept, kept when
+ *   every earlier neighbour is removed.  remaining [1] i32 is INCREASED by the number of points left undecided.  The grid's
+ *   cell must be >= dst * (1 + 1e-6).
+ * dmvs_cloud_nn: one pass of the bounded nearest neighbour that MaxDistCP.m:31-33 computes block by block, on one grid level:
+ *   to_xyz key-sorted with ukeys / ustart; queries q_xyz[q_idx[k]], k < nq (q_idx NULL: k), which must lie inside the grid.
+ *   Rings of cells outwards, at most `rings`; best2 [N_from] f64 (in / out, +inf at the start) and nn [N_from] i32 (in / out,
+ *   optional) carry the best squared distance / its point to the next, coarser level; resolved [nq] u8 = 1 when no unexamined
+ *   point can be nearer or the searched radius reached max_dist, and then dist [N_from] f64 = min(sqrt(best2), max_dist).
+ *   examined: NULL or one u64 counter of distances evaluated.
+ * dmvs_cloud_in_mask: DataInMask, PointCompareMain.m:33-42: v = floor((p - bb0) / res + 1 + 0.5) (MATLAB's round on every value
+ *   that can land in range), 1 <= v <= mask_dims and mask[vx - 1][vy - 1][vz - 1] != 0 (u8 volume, z fastest).
+ * dmvs_cloud_above_plane: StlAbovePlane, PointCompareMain.m:54: p0 x + p1 y + p2 z + p3 > 0.
+ * dmvs_cloud_in_box: the from-points MaxDistCP.m:10-18 searches at all: lo <= p < hi on every axis. */
+int dmvs_cloud_cell_keys(const float* xyz, int n, const double* origin3, double cell, const int* dims3, long long* keys,
+                         dmvs_stream_t stream);
+int dmvs_cloud_cell_runs(const long long* ukeys, const int* ustart, int M, const int* dims3, int* runs, dmvs_stream_t stream);
+int dmvs_cloud_thin_round(const float* xyz, const int* prio, const int* cell_of, const int* runs, unsigned char* state,
+                          const int* todo, int n_todo, double dst, int* remaining, dmvs_stream_t stream);
+int dmvs_cloud_nn(const float* to_xyz, const long long* ukeys, const int* ustart, int M, const double* origin3, double cell,
+                  const int* dims3, const float* q_xyz, const int* q_idx, int nq, int rings, double max_dist, double* best2,
+                  int* nn, double* dist, unsigned char* resolved, unsigned long long* examined, dmvs_stream_t stream);
+int dmvs_cloud_in_mask(const float* xyz, int n, const double* bb0, double res, const unsigned char* mask, const int* mask_dims3,
+                       unsigned char* out, dmvs_stream_t stream);
+int dmvs_cloud_above_plane(const float* xyz, int n, const double* plane4, unsigned char* out, dmvs_stream_t stream);
+int dmvs_cloud_in_box(const float* xyz, int n, const double* lo3, const double* hi3, unsigned char* out, dmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
