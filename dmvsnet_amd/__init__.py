@@ -11,6 +11,9 @@ from . import eval_io  # noqa: F401  (PFM / cam I/O, eval dataset, Model.test st
 from . import fusion   # noqa: F401  (geometric-consistency fusion filter, PLY)
 from . import cloud_eval  # noqa: F401  (DTU accuracy / completeness of a fused cloud)
 from .cloud_eval import evaluate_dtu, max_dist_cp, point_compare, reduce_points, scan_stats  # noqa: F401
+from . import validate  # noqa: F401  (Model.validate: dual-depth loss and depth metrics on ground truth)
+from .validate import AbsDepthError_metrics, DTUValDataset, Thres_metrics, mvs_loss, run_validate  # noqa: F401
 
 __all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFeatures", "shard_source_views", "eval_io", "fusion",
-           "cloud_eval", "reduce_points", "max_dist_cp", "point_compare", "scan_stats", "evaluate_dtu"]
+           "cloud_eval", "reduce_points", "max_dist_cp", "point_compare", "scan_stats", "evaluate_dtu", "validate", "mvs_loss",
+           "AbsDepthError_metrics", "Thres_metrics", "DTUValDataset", "run_validate"]

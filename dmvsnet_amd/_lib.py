@@ -78,6 +78,8 @@ SIGNATURES = {
     "dmvs_cloud_in_mask": (_i, [_p, _i, _p, _d, _p, _p, _p, _p]),
     "dmvs_cloud_above_plane": (_i, [_p, _i, _p, _p, _p]),
     "dmvs_cloud_in_box": (_i, [_p, _i, _p, _p, _p, _p]),
+    "dmvs_dual_depth_loss_workspace": (ctypes.c_long, [_i, _i, _i]),
+    "dmvs_dual_depth_loss": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
     "dmvs_prob_regress": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p]),
     "dmvs_depth_select": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "dmvs_depth_regress": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

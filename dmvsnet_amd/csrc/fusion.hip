@@ -311,3 +311,6 @@ extern "C" int dmvs_fuse_emit(const unsigned char* masks, const double* depth_av
 
 // N5: the point-cloud evaluation kernels (an extension of N4: what becomes of the fused cloud) live in a header of their own
 #include "cloud_eval.h"
+
+// N6: validation mode (what the depth maps are worth against ground truth): the dual-depth loss and the depth metrics
+#include "validate.h"

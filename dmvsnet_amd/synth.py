@@ -23,6 +23,7 @@ import torch
 __all__ = [
     "synth_fusion_scene",
     "synth_cloud_scene",
+    "synth_val_scene",
     "synth_images",
     "synth_cameras",
     "synth_depth_values",
@@ -245,3 +246,61 @@ def synth_cloud_scene(seed: int, n_data: int, n_stl: int, noise: float = 0.12, o
     obs = np.ascontiguousarray(band & inner, dtype=np.uint8)
     plane = np.array([0.02, -0.015, 1.0, 0.012 * L], dtype=np.float64)
     return dict(data=data, stl=stl, ObsMask=obs, BB=bb, Res=res, P=plane)
+
+
+def synth_val_scene(root: str, seed: int = 0, V: int = 3, lights: int = 2, scan: str = "scan1", raw_hw=(1200, 1600)) -> Dict[str, object]:
+    """Write a small tree in the DTU TRAINING layout (what datasets/dtu_yao.py reads) under ``root``: one scan, ``V`` views,
+    ``lights`` light conditions.
+
+      Cameras/pair.txt, Cameras/train/%08d_cam.txt   intrinsics at 1/4 scale (synth_cameras' stage 1), depth line "425.0 2.5"
+      Rectified/<scan>_train/rect_%03d_<light>_r5000.png   512 x 640 RGB (view id + 1 in the name)
+      Depths_raw/<scan>/depth_map_%04d.pfm           raw ground truth ``raw_hw`` (1200 x 1600: the loader halves it and crops
+                                                     512 x 640 from the middle): a smooth surface 450..800 mm
+      Depths_raw/<scan>/depth_visual_%04d.png        8-bit mask source (valid > 10): ragged holes, a dark band of values <= 10
+      val.txt                                        the scan list
+
+    Returns {"listfile", "scan", "views", "lights"}; the loader's metas are views x 7 lights unless told ``lights``."""
+    import os
+
+    from PIL import Image
+
+    from . import eval_io
+
+    H, W = 512, 640
+    os.makedirs(os.path.join(root, "Cameras", "train"), exist_ok=True)
+    os.makedirs(os.path.join(root, "Rectified", scan + "_train"), exist_ok=True)
+    os.makedirs(os.path.join(root, "Depths_raw", scan), exist_ok=True)
+    cams = synth_cameras(H, W, V)["stage1"][0].numpy()
+    with open(os.path.join(root, "Cameras", "pair.txt"), "w") as f:
+        f.write("{}\n".format(V))
+        for v in range(V):
+            others = [(v + k) % V for k in range(1, V)]
+            f.write("{}\n{} {}\n".format(v, len(others), " ".join("{} {}".format(o, 100.0 - k) for k, o in enumerate(others))))
+    for v in range(V):
+        with open(os.path.join(root, "Cameras", "train", "{:0>8}_cam.txt".format(v)), "w") as f:
+            f.write("extrinsic\n")
+            for i in range(4):
+                f.write(" ".join(str(cams[v, 0, i, j]) for j in range(4)) + " \n")
+            f.write("\nintrinsic\n")
+            for i in range(3):
+                f.write(" ".join(str(cams[v, 1, i, j]) for j in range(3)) + " \n")
+            f.write("\n425.0 2.5\n")
+        g = _rng(seed, f"val.gt.{v}")
+        rh, rw = raw_hw
+        depth = np.float32(450.0) + np.float32(350.0) * _upsample_bilinear_np(g.random((6, 8), dtype=np.float32), rh, rw)
+        vis = (g.random((rh // 8, rw // 8), dtype=np.float32) > 0.12).astype(np.uint8).repeat(8, 0).repeat(8, 1) * 200
+        vis[g.random((rh, rw), dtype=np.float32) < 0.02] = 10                     # single-pixel holes, exactly at the threshold
+        vis[rh // 2 - 3:rh // 2 + 4, :] = 7                                        # a dark band through the crop
+        depth[vis <= 10] = 0.0
+        eval_io.save_pfm(os.path.join(root, "Depths_raw", scan, "depth_map_{:0>4}.pfm".format(v)), depth)
+        Image.fromarray(vis).save(os.path.join(root, "Depths_raw", scan, "depth_visual_{:0>4}.png".format(v)))
+    for light in range(lights):
+        imgs = synth_images(H, W, V, seed=seed + 17 * light)[0].numpy()
+        for v in range(V):
+            a = np.clip(np.transpose(imgs[v], (1, 2, 0)) * 255.0, 0, 255).astype(np.uint8)
+            Image.fromarray(a).save(os.path.join(root, "Rectified", scan + "_train", "rect_{:0>3}_{}_r5000.png".format(v + 1, light)),
+                                    compress_level=1)
+    listfile = os.path.join(root, "val.txt")
+    with open(listfile, "w") as f:
+        f.write(scan + "\n")
+    return {"listfile": listfile, "scan": scan, "views": V, "lights": lights}

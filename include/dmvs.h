@@ -25,7 +25,7 @@ extern "C" {
 
 typedef void* dmvs_stream_t; /* hipStream_t */
 
-#define DMVS_VERSION 140 /* 0.1.4: + N5 dmvs_cloud_cell_keys / _cell_runs / _thin_round / _nn / _in_mask / _above_plane / _in_box (additive, same version); 0.1.4 (r06): + dmvs_prob_regress / dmvs_depth_select (`prob` -> K4); 0.1.3 (r06): + K3z dmvs_conv3d_zmarch / _weight_floats / dmvs_pack_conv_weights_zmarch, + the bf16-split probe dmvs_conv3d_split_probe / _weight_floats / dmvs_pack_conv_weights_split; 0.1.2 (r05): + K3r dmvs_conv3d_coarse / _weight_floats / dmvs_pack_conv_weights_coarse; 0.1.1: DMVS_OUT_Q4 moved to bit 3 (value 8); bit 2 (value 4, r02's DMVS_OUT_HWC2: two
+#define DMVS_VERSION 140 /* 0.1.4: + N6 dmvs_dual_depth_loss / _workspace (additive, same version); + N5 dmvs_cloud_cell_keys / _cell_runs / _thin_round / _nn / _in_mask / _above_plane / _in_box (additive, same version); 0.1.4 (r06): + dmvs_prob_regress / dmvs_depth_select (`prob` -> K4); 0.1.3 (r06): + K3z dmvs_conv3d_zmarch / _weight_floats / dmvs_pack_conv_weights_zmarch, + the bf16-split probe dmvs_conv3d_split_probe / _weight_floats / dmvs_pack_conv_weights_split; 0.1.2 (r05): + K3r dmvs_conv3d_coarse / _weight_floats / dmvs_pack_conv_weights_coarse; 0.1.1: DMVS_OUT_Q4 moved to bit 3 (value 8); bit 2 (value 4, r02's DMVS_OUT_HWC2: two
                             PIXEL-MAJOR halves) is retired and rejected with DMVS_EUNSUPPORTED -- a caller built against
                             version 100 can no longer get the quad-planar layout silently; dmvs_tune("k1_variant") is
                             gone (the launch variant is an argument of dmvs_warp_corr_q4) */
@@ -429,6 +429,29 @@ int dmvs_cloud_in_mask(const float* xyz, int n, const double* bb0, double res, c
                        unsigned char* out, dmvs_stream_t stream);
 int dmvs_cloud_above_plane(const float* xyz, int n, const double* plane4, unsigned char* out, dmvs_stream_t stream);
 int dmvs_cloud_in_box(const float* xyz, int n, const double* lo3, const double* hi3, unsigned char* out, dmvs_stream_t stream);
+
+/* N6: validation mode (csrc/validate.h, host side dmvsnet_amd/validate.py) -- one stage of the dual-depth regression loss and / or
+ * the depth metrics against ground truth, in two launches (the fused pass and a one-workgroup finishing kernel).  Replaces the
+ * arithmetic of loss.py:5-80 (mvs_loss, mode "regression"), loss.py:106-159 (Monte_Carlo_sampling_loss mode "center",
+ * regression_loss) and tools.py:159-201 (AbsDepthError_metrics, Thres_metrics).  Unlike the entries above it takes a batch.
+ *   dsp_main, dsp_refine [B][4][h][w] (depth_sub_plus, depth_sub_plus_refine), both or neither (NULL: metrics only);
+ *   gt, mask [B][h][w], a pixel is valid iff mask > 0.5; depth [B][h][w] or NULL (NULL: loss only); weight: the stage's dlossw;
+ *   thres3: HOST array of the three error thresholds (needed with depth).
+ *   Per-element terms are fp32 in the reference's operation order, sl1(d) = |d| < 1 ? 0.5 d d : |d| - 0.5, term = sl1 * weight;
+ *   invalid pixels and 2x2 cells (any corner invalid) are selected out, never multiplied by zero; sums are fp64, added in a fixed
+ *   order, each mean rounded to fp32 once; cells do not straddle images; the cell centre is (((nw + ne) + sw) + se) * 0.25.
+ *   total_loss [1]: += ((2 m0 + 2 m1) + m2 + m3 + (((m4 + m5) + m6) + m7)) of the main outputs, then of the refine outputs, fp32,
+ *     with terms16 [2][8] = m0..m7: mean over 2n of channels {0,1}, of {2,3}; var small, var huge over n; the four centre terms over
+ *     n_cells (surfaces where(cm, min, max), where(~cm, min, max) of channels {0,1}, then of {2,3}; cm = row % 2 == col % 2).
+ *     An empty mask gives NaN.  counts2 [2] i64: n, n_cells.  At least one of the three is required with dsp_*.
+ *   image_sums [B][5] f64: sum |depth - gt|, n_valid, n with |depth - gt| > thres3[0..2] per image; metrics4 [4]: the batch means
+ *     of (abs error, the three rates), an empty image counting 0.  At least one of the two is required with depth.
+ *   workspace: dmvs_dual_depth_loss_workspace(B, h, w) doubles (one row per workgroup), overwritten.
+ * DMVS_EINVAL on h < 2, w < 2, B < 1 or a missing pointer. */
+long dmvs_dual_depth_loss_workspace(int B, int h, int w);
+int dmvs_dual_depth_loss(const float* dsp_main, const float* dsp_refine, const float* gt, const float* mask, const float* depth,
+                         int B, int h, int w, float weight, const float* thres3, double* workspace, float* total_loss,
+                         float* terms16, long long* counts2, double* image_sums, float* metrics4, dmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
