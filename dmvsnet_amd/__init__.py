@@ -7,6 +7,8 @@ library behind include/dmvs.h; there is no CPU or PyTorch fallback.
 """
 from .mvsnet import CostAgg, CostRegNet, DepthNet, FeatureNet, MVSNet, ViewFeatures, shard_source_views  # noqa: F401
 
+from .costagg import DiffCostAgg, cost_agg  # noqa: F401  (differentiable cost aggregation: K1 + its backward)
+
 from . import eval_io  # noqa: F401  (PFM / cam I/O, eval dataset, Model.test step 1)
 from . import fusion   # noqa: F401  (geometric-consistency fusion filter, PLY)
 from . import cloud_eval  # noqa: F401  (DTU accuracy / completeness of a fused cloud)
@@ -16,4 +18,4 @@ from .validate import AbsDepthError_metrics, DTUValDataset, Thres_metrics, mvs_l
 
 __all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFeatures", "shard_source_views", "eval_io", "fusion",
            "cloud_eval", "reduce_points", "max_dist_cp", "point_compare", "scan_stats", "evaluate_dtu", "validate", "mvs_loss",
-           "AbsDepthError_metrics", "Thres_metrics", "DTUValDataset", "run_validate"]
+           "AbsDepthError_metrics", "Thres_metrics", "DTUValDataset", "run_validate", "DiffCostAgg", "cost_agg"]

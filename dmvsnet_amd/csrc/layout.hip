@@ -49,6 +49,29 @@ extern "C" int dmvs_nchw_to_hwc(const float* src, int c0, int C, int H, int W, f
     return dmvs_planar_to_hwc(src, (long)H * W, c0, C, H, W, dst, s);
 }
 
+// ------------------------------------------------------------------ NCHW slice -> quad-planar
+// [C_total][H][W] planar channels c0..c0+C (any channel stride: a torch `split` half is a view with the parent's stride)
+// -> [C/4][H][W][4], the layout K1's product kernel samples.  A lane owns a pixel of one quad: four coalesced plane
+// reads, one 16-byte store; consecutive lanes store consecutive quads.
+__global__ __launch_bounds__(256) void nchw_to_q4_kernel(const float* __restrict__ src, long chan_stride, int c0, int HW,
+                                                         float4_t* __restrict__ dst) {
+    const int p = blockIdx.x * 256 + threadIdx.x, q = blockIdx.y;
+    if (p >= HW) return;
+    const float* s = src + (size_t)(c0 + 4 * q) * chan_stride + p;
+    dst[(size_t)q * HW + p] = float4_t{s[0], s[chan_stride], s[2 * chan_stride], s[3 * chan_stride]};
+}
+
+extern "C" int dmvs_nchw_to_q4(const float* src, long chan_stride, int c0, int C, int H, int W, float* dst_q4,
+                               dmvs_stream_t s) {
+    if (!src || !dst_q4 || H <= 0 || W <= 0 || c0 < 0 || chan_stride < (long)H * W) return DMVS_EINVAL;
+    if (((uintptr_t)dst_q4 & 15) != 0) return DMVS_EINVAL;
+    if (C != 8 && C != 16 && C != 32) return DMVS_EUNSUPPORTED;
+    const int HW = H * W;
+    nchw_to_q4_kernel<<<dim3(ceil_div(HW, 256), C / 4), 256, 0, (hipStream_t)s>>>(src, chan_stride, c0, HW,
+                                                                                 reinterpret_cast<float4_t*>(dst_q4));
+    DMVS_LAUNCH_CHECK();
+}
+
 // ------------------------------------------------------------------ image ingest
 // Decoded image -> the [3][H][W] fp32 planes FeatureNet reads, bit-identical to the eval loader (eval_io.MVSDataset):
 // uint8 -> float through the host's 256-entry table (np.float32(u) / 255.0), then eval_io.resize_linear's two passes

@@ -44,6 +44,46 @@ __device__ __forceinline__ float hyp_plane(const WarpArgs& a, int d, size_t plan
     return a.depth ? a.depth[(size_t)d * plane + pix] : a.base[pix] + (float)d * step;
 }
 
+// One sample of view P (12 floats: rot 9 + trans 3) at pixel (fx, fy) and hypothesis `depth`, in the reference's op order:
+// rot*(x,y,1), *depth, +trans, z==0 -> +1e-5, /z, normalise to [-1,1], ATen's un-normalise (align_corners=True), then the
+// four bilinear taps.  Shared by the generic forward kernel below and by the backward kernels (warp_corr_bwd.h), so that
+// a gradient is taken at exactly the taps this forward samples.  wm1 = W - 1, hm1 = H - 1, half_w = wm1 / 2, half_h = hm1 / 2.
+struct RefTaps {
+    int x0, x1, y0, y1;            // tap coordinates, clamped into the image for addressing
+    bool x0in, x1in, y0in, y1in;   // per-axis range tests: a tap outside the image has weight 0 (padding_mode="zeros")
+    float w00, w01, w10, w11;      // w<row><col>
+};
+__device__ __forceinline__ RefTaps ref_order_taps(const float* P, float fx, float fy, float depth, float wm1, float hm1,
+                                                  float half_w, float half_h) {
+    RefTaps t;
+    // rot @ (x, y, 1)   (module.py:233)
+    const float rx = fmaf(P[1], fy, P[0] * fx) + P[2];
+    const float ry = fmaf(P[4], fy, P[3] * fx) + P[5];
+    const float rz = fmaf(P[7], fy, P[6] * fx) + P[8];
+    // * depth + trans   (module.py:234-236)
+    const float px = rx * depth + P[9];
+    const float py = ry * depth + P[10];
+    float pz = rz * depth + P[11];
+    if (pz == 0.0f) pz += 0.00001f;  // module.py:237
+    // perspective divide, normalise (module.py:239-241), ATen un-normalise (align_corners=True)
+    const float gx = (px / pz) / half_w - 1.0f;
+    const float gy = (py / pz) / half_h - 1.0f;
+    const float ix = ((gx + 1.0f) / 2.0f) * wm1;
+    const float iy = ((gy + 1.0f) / 2.0f) * hm1;
+    const float x0f = floorf(ix), y0f = floorf(iy);
+    const float tx = ix - x0f, ty = iy - y0f;
+    // bounds per tap; out-of-range coordinates are clamped for addressing and get weight 0
+    t.x0in = (x0f >= 0.f) && (x0f <= wm1); t.x1in = (x0f >= -1.f) && (x0f <= wm1 - 1.f);
+    t.y0in = (y0f >= 0.f) && (y0f <= hm1); t.y1in = (y0f >= -1.f) && (y0f <= hm1 - 1.f);
+    t.x0 = (int)fminf(fmaxf(x0f, 0.f), wm1); t.x1 = (int)fminf(fmaxf(x0f + 1.f, 0.f), wm1);
+    t.y0 = (int)fminf(fmaxf(y0f, 0.f), hm1); t.y1 = (int)fminf(fmaxf(y0f + 1.f, 0.f), hm1);
+    t.w00 = (t.x0in && t.y0in) ? (1.f - tx) * (1.f - ty) : 0.f;
+    t.w01 = (t.x1in && t.y0in) ? tx * (1.f - ty) : 0.f;
+    t.w10 = (t.x0in && t.y1in) ? (1.f - tx) * ty : 0.f;
+    t.w11 = (t.x1in && t.y1in) ? tx * ty : 0.f;
+    return t;
+}
+
 template <int C, int DCHUNK>
 __global__ __launch_bounds__(256) void warp_corr_kernel(WarpArgs a) {
     constexpr int LPP = C / 4;          // lanes per pixel
@@ -68,31 +108,9 @@ __global__ __launch_bounds__(256) void warp_corr_kernel(WarpArgs a) {
         float acc0 = 0.f, acc1 = 0.f;
         for (int v = 0; v < a.nsrc; ++v) {
             const float* P = a.proj + v * 12;  // uniform -> scalar loads
-            // rot @ (x, y, 1)   (module.py:233)
-            const float rx = fmaf(P[1], fy, P[0] * fx) + P[2];
-            const float ry = fmaf(P[4], fy, P[3] * fx) + P[5];
-            const float rz = fmaf(P[7], fy, P[6] * fx) + P[8];
-            // * depth + trans   (module.py:234-236)
-            const float px = rx * depth + P[9];
-            const float py = ry * depth + P[10];
-            float pz = rz * depth + P[11];
-            if (pz == 0.0f) pz += 0.00001f;  // module.py:237
-            // perspective divide, normalise (module.py:239-241), ATen un-normalise (align_corners=True)
-            const float gx = (px / pz) / half_w - 1.0f;
-            const float gy = (py / pz) / half_h - 1.0f;
-            const float ix = ((gx + 1.0f) / 2.0f) * wm1;
-            const float iy = ((gy + 1.0f) / 2.0f) * hm1;
-            const float x0f = floorf(ix), y0f = floorf(iy);
-            const float tx = ix - x0f, ty = iy - y0f;
-            // bounds per tap; out-of-range coordinates are clamped for addressing and get weight 0
-            const bool x0in = (x0f >= 0.f) && (x0f <= wm1), x1in = (x0f >= -1.f) && (x0f <= wm1 - 1.f);
-            const bool y0in = (y0f >= 0.f) && (y0f <= hm1), y1in = (y0f >= -1.f) && (y0f <= hm1 - 1.f);
-            const int x0 = (int)fminf(fmaxf(x0f, 0.f), wm1), x1 = (int)fminf(fmaxf(x0f + 1.f, 0.f), wm1);
-            const int y0 = (int)fminf(fmaxf(y0f, 0.f), hm1), y1 = (int)fminf(fmaxf(y0f + 1.f, 0.f), hm1);
-            const float w00 = (x0in && y0in) ? (1.f - tx) * (1.f - ty) : 0.f;
-            const float w01 = (x1in && y0in) ? tx * (1.f - ty) : 0.f;
-            const float w10 = (x0in && y1in) ? (1.f - tx) * ty : 0.f;
-            const float w11 = (x1in && y1in) ? tx * ty : 0.f;
+            const RefTaps tp = ref_order_taps(P, fx, fy, depth, wm1, hm1, half_w, half_h);
+            const int x0 = tp.x0, x1 = tp.x1, y0 = tp.y0, y1 = tp.y1;
+            const float w00 = tp.w00, w01 = tp.w01, w10 = tp.w10, w11 = tp.w11;
             const float* S = a.src[v] + lane_c * 4;
             const float4_t s00 = *reinterpret_cast<const float4_t*>(S + ((size_t)y0 * W + x0) * a.pix_stride);
             const float4_t s01 = *reinterpret_cast<const float4_t*>(S + ((size_t)y0 * W + x1) * a.pix_stride);
@@ -672,3 +690,7 @@ extern "C" int dmvs_warp_corr_q4_f16(const void* ref_q4h, const void* const* src
     return warp_corr_q4_entry(ref_q4h, src_q4h, nsrc, proj12, depth_dhw, base_hw, step, sim_2dhw, C, D, H, W, accumulate,
                               variant, true, stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// K1b: the backward kernels (dRef gather, dSrc scatter) and dmvs_warp_corr_backward
+#include "warp_corr_bwd.h"

@@ -303,6 +303,43 @@ def hwc_to_q4(f_hwc: torch.Tensor) -> torch.Tensor:
     return f_hwc.view(H, W, C // 4, 4).permute(2, 0, 1, 3).contiguous()
 
 
+def nchw_to_q4(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src [C,H,W] planar (one sample of a torch feature map; may be a channel slice of a wider map, e.g. a ``split`` half:
+    rows contiguous, any channel stride) -> [C/4,H,W,4] quad-planar.  Layout glue: the launch is not logged."""
+    if not src.is_cuda:
+        raise _lib.DmvsError(f"dmvsnet_amd kernels need tensors on a HIP device (no CPU fallback); got {src.device}")
+    if src.dtype != torch.float32 or src.dim() != 3:
+        raise _lib.DmvsError(f"nchw_to_q4: expected a float32 [C,H,W] map, got {src.dtype} {tuple(src.shape)}")
+    C, H, W = src.shape
+    if src.stride(2) != 1 or src.stride(1) != W or src.stride(0) < H * W:
+        src = src.contiguous()
+    dst = torch.empty((C // 4, H, W, 4), dtype=torch.float32, device=src.device) if out is None else out
+    _req(dst)
+    assert tuple(dst.shape) == (C // 4, H, W, 4), tuple(dst.shape)
+    _lib.check(_lib.load().dmvs_nchw_to_q4(_ptr(src), src.stride(0), 0, C, H, W, _ptr(dst), _stream()), "dmvs_nchw_to_q4")
+    return dst
+
+
+def warp_corr_backward(ref_q4: torch.Tensor, src_q4: Sequence[torch.Tensor], proj12: torch.Tensor, depth_dhw: torch.Tensor,
+                       gsim: torch.Tensor, gref: Optional[torch.Tensor], gsrc: Sequence[Optional[torch.Tensor]]) -> None:
+    """K1b.  Quad-planar features, gsim [2,D,H,W]; writes gref [C,H,W] (or None: skipped) and ADDS into the gsrc[v] [C,H,W]
+    (zero-initialised by the caller; None: that view is skipped).  Not logged as a launch family."""
+    live = [g for g in gsrc if g is not None]
+    _req(ref_q4, proj12, depth_dhw, gsim, gref, *src_q4, *live)
+    D, H, W = depth_dhw.shape
+    C = 4 * ref_q4.shape[0]
+    nsrc = len(src_q4)
+    assert len(gsrc) == nsrc and proj12.shape[0] == nsrc and tuple(gsim.shape) == (2, D, H, W)
+    for g in (gref, *live):
+        assert g is None or tuple(g.shape) == (C, H, W), (tuple(g.shape), (C, H, W))
+    if gref is None and not live:
+        return
+    arr = (ctypes.c_void_p * nsrc)(*[s.data_ptr() for s in src_q4])
+    garr = (ctypes.c_void_p * nsrc)(*[None if g is None else g.data_ptr() for g in gsrc])
+    _lib.check(_lib.load().dmvs_warp_corr_backward(_ptr(ref_q4), arr, nsrc, _ptr(proj12), _ptr(depth_dhw), _ptr(gsim), _ptr(gref),
+                                                   garr, C, D, H, W, _stream()), "dmvs_warp_corr_backward")
+
+
 def warp_corr(ref: torch.Tensor, src: Sequence[torch.Tensor], proj12: torch.Tensor, depth_dhw: torch.Tensor,
               out: Optional[torch.Tensor] = None, accumulate: bool = False, C: Optional[int] = None,
               pix_stride: Optional[int] = None, variant: int = 0, family: str = "warp_corr",

@@ -179,6 +179,30 @@ int dmvs_warp_corr_q4_f16(const void* ref_q4h, const void* const* src_q4h, int n
                           const float* depth_dhw, const float* base_hw, const float* step, float* sim_2dhw,
                           int C, int D, int H, int W, int accumulate, int variant, dmvs_stream_t stream);
 
+/* K1b: backward of the fused warp + correlation with respect to the FEATURE MAPS.  Differentiates CostAgg.forward
+ * (mvsnet.py:111-153) over homo_warping (module.py:212-251); the sampling grid is built under torch.no_grad()
+ * (module.py:222-243), so the cameras and the hypotheses receive no gradient -- there is none to compute.  With
+ * G = gsim_2dhw and W_v = source view v sampled bilinearly (zeros padding, align_corners=True):
+ *   gref_chw[c][y][x]         = (2/C) sum_v sum_d G[c & 1][d][y][x] * W_v[c][d][y][x]       (plain stores, reproducible)
+ *   gsrc_chw[v][c][tap]      += w_tap * (2/C) * G[c & 1][d][y][x] * ref[c][y][x]            (fp32 global atomics)
+ *   ref_q4, src_q4 (host)     quad-planar [C/4][H][W][4] features, as dmvs_warp_corr_q4
+ *   proj12, depth_dhw         as dmvs_warp_corr (taps in the reference's op order, the generic kernel's routine)
+ *   gsim_2dhw                 [2][D][H][W] upstream gradient
+ *   gref_chw                  [C][H][W] planar, or NULL: the reference-gradient kernel is skipped
+ *   gsrc_chw (host)           array of nsrc device pointers to [C][H][W] planar gradients that the CALLER has zeroed, or
+ *                             NULL; a NULL entry skips that view; all NULL skips the source-gradient kernel
+ * The source gradients depend on the arrival order of the atomics: equal run to run only to fp32 rounding.
+ * C in {8,16,32}; 1 <= nsrc <= DMVS_MAX_SRC_VIEWS; any D. */
+int dmvs_warp_corr_backward(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
+                            const float* depth_dhw, const float* gsim_2dhw, float* gref_chw, float* const* gsrc_chw,
+                            int C, int D, int H, int W, dmvs_stream_t stream);
+
+/* [C_total][H][W] planar slice c0..c0+C with a channel stride of chan_stride floats -> quad-planar [C/4][H][W][4]:
+ * layout glue between torch feature maps (module.py:326-336: the stageK / stageK_c `split` halves are views that keep
+ * the parent's channel stride; a batch sample is a pointer offset) and dmvs_warp_corr_q4 / dmvs_warp_corr_backward.
+ * No arithmetic.  C in {8,16,32}; dst_q4 16-byte aligned. */
+int dmvs_nchw_to_q4(const float* src, long chan_stride, int c0, int C, int H, int W, float* dst_q4, dmvs_stream_t stream);
+
 /* K2: direct LDS-tiled 3D convolution / transposed convolution, fp32 VALU, fused epilogue
  *        y = conv(x) * scale[co] + shift[co];  relu;  y += skip
  * which is Conv3d/Deconv3d + BatchNorm(eval) + ReLU (module.py:151-157, 196-202) followed by the

@@ -1,0 +1,188 @@
+#!/usr/bin/env python
+"""Time forward + backward of the differentiable cost aggregation (dmvsnet_amd.cost_agg: K1 + K1b) against the same operator
+as ATen ops with grid_sample, for the six cost-aggregation passes of a training step, per sample (batch 1).
+
+Recipes: DTU training (512 x 640, 5 views, 48 / 32 / 8 planes + three 4-plane refine passes; scripts/train.sh) and BlendedMVS
+fine-tuning (576 x 768, 7 views; scripts/blendedmvs_finetune.sh).  Both arms run in one process on one GPU, on the same
+tensors; every arm is warmed, and the timed windows alternate with the order swapped every round (the K1 run-order lesson,
+DESIGN.md section 7 item 5).  Per pass and arm:
+  ms               forward + backward (gradients to every feature map), device events around --reps repetitions, per
+                   repetition; min / median / max over the windows
+  peak_mb          torch.cuda.max_memory_allocated over one forward + backward, minus what was allocated before it
+and for the fused arm alone the two backward kernels apart (bwd_ref_ms, bwd_src_ms: dmvs_warp_corr_backward with one output
+switched off), with the atomic payload of the source-gradient kernel (4 taps * C * 4 B per sample, all samples counted, as
+the sizing in docs/kernels/K1b_warp_corr_backward.md does) over its time; for the ATen arm grid_sample's backward alone
+(aten_grid_bwd_ms, all source views).  One JSON line; --md writes the table of profiles/costagg_train.md.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT]
+
+RECIPES = {"dtu_512x640_5v": (512, 640, 5), "blendedmvs_576x768_7v": (576, 768, 7)}
+PASSES = (("s1.main", 32, 48, 4), ("s1.refine", 32, 4, 4), ("s2.main", 16, 32, 2), ("s2.refine", 16, 4, 2),
+          ("s3.main", 8, 8, 1), ("s3.refine", 8, 4, 1))   # name, C, D, image size divisor
+
+
+def aten_grid(pairs, v, depth):
+    """The reference's sampling grid of source view v (module.py:222-243), built without a graph."""
+    with torch.no_grad():
+        B, D, H, W = depth.shape
+        comp = lambda p: torch.cat((p[:, 1, :3, :3] @ p[:, 0, :3, :4], p[:, 0, 3:]), 1)   # noqa: E731
+        P = comp(pairs[:, v]) @ torch.inverse(comp(pairs[:, 0]))
+        yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float32, device=depth.device),
+                                torch.arange(W, dtype=torch.float32, device=depth.device), indexing="ij")
+        xyz = torch.stack((xx.reshape(-1), yy.reshape(-1), torch.ones_like(xx.reshape(-1))))
+        pts = (P[:, :3, :3] @ xyz).unsqueeze(2) * depth.view(B, 1, D, H * W) + P[:, :3, 3].view(B, 3, 1, 1)
+        z = torch.where(pts[:, 2] == 0, pts[:, 2] + 1e-5, pts[:, 2])
+        return torch.stack((pts[:, 0] / z / ((W - 1) / 2) - 1, pts[:, 1] / z / ((H - 1) / 2) - 1), 3).view(B, D * H, W, 2)
+
+
+def aten_cost_agg(feats, pairs, depth):
+    """CostAgg.forward in train mode (mvsnet.py:111-153): one warped volume and one grid per source view stay alive."""
+    B, C, H, W = feats[0].shape
+    D = depth.shape[1]
+    total = 0
+    for v in range(1, len(feats)):
+        warped = F.grid_sample(feats[v], aten_grid(pairs, v, depth), mode="bilinear", padding_mode="zeros", align_corners=True)
+        total = total + (warped.view(B, C // 2, 2, D, H, W) * feats[0].view(B, C // 2, 2, 1, H, W)).mean(1)
+    return total
+
+
+def spread(ts):
+    return dict(min=min(ts), median=float(np.median(ts)), max=max(ts), n=len(ts))
+
+
+def window(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def peak_mb(fn):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--windows", type=int, default=4)
+    ap.add_argument("--recipes", default=",".join(RECIPES))
+    ap.add_argument("--md", default=None, help="also write the result table (markdown) to this file")
+    args = ap.parse_args()
+
+    from dmvsnet_amd import cost_agg, ops, synth
+    assert torch.cuda.is_available(), "the benchmark needs the MI355X"
+    dev = torch.device("cuda:0")
+    out = dict(bench="costagg_train", device=torch.cuda.get_device_name(0), reps=args.reps, windows=args.windows, recipes={})
+    for recipe in args.recipes.split(","):
+        Hf, Wf, V = RECIPES[recipe]
+        cams = synth.synth_cameras(Hf, Wf, V)
+        rows = {}
+        for ipass, (name, C, D, div) in enumerate(PASSES):
+            H, W = Hf // div, Wf // div
+            g = torch.Generator(device="cpu").manual_seed(100 * V + ipass)
+            feats = [torch.randn(1, C, H, W, generator=g).to(dev).requires_grad_(True) for _ in range(V)]
+            pairs = cams["stage{}".format({4: 1, 2: 2, 1: 3}[div])].to(dev)
+            # main passes: planes across the depth range; refine passes: 4 planes around a smooth prior
+            step = (240.0 / D) if D > 4 else 2.65 * div
+            depth = (560.0 + step * torch.arange(D, dtype=torch.float32).view(1, D, 1, 1) + 5.0 * torch.randn(1, D, H, W, generator=g)).to(dev)
+            gsim = torch.randn(1, 2, D, H, W, generator=g).to(dev)
+
+            def fused():
+                torch.autograd.grad(cost_agg(feats, pairs, depth), feats, gsim)
+
+            def aten():
+                torch.autograd.grad(aten_cost_agg(feats, pairs, depth), feats, gsim)
+
+            arms = {"fused": fused, "aten": aten}
+            for fn in arms.values():
+                fn()
+            torch.cuda.synchronize()
+            ms = {k: [] for k in arms}
+            for w in range(args.windows):
+                for k in (("fused", "aten") if w % 2 == 0 else ("aten", "fused")):
+                    ms[k].append(window(arms[k], args.reps))
+            r = {k + "_ms": spread(v) for k, v in ms.items()}
+            r.update({k + "_peak_mb": peak_mb(fn) for k, fn in arms.items()})
+            r["aten_over_fused"] = r["aten_ms"]["median"] / r["fused_ms"]["median"]
+
+            # the fused arm's kernels apart
+            with torch.no_grad():
+                q4 = [ops.nchw_to_q4(f[0]) for f in feats]
+                proj12 = ops.relative_proj(pairs[0].contiguous())
+                gref = torch.empty((C, H, W), device=dev)
+                gsrc = [torch.zeros((C, H, W), device=dev) for _ in range(V - 1)]
+                none = [None] * (V - 1)
+                parts = {"fwd_ms": lambda: ops.warp_corr(q4[0], q4[1:], proj12, depth[0], layout="q4"),
+                         "bwd_ref_ms": lambda: ops.warp_corr_backward(q4[0], q4[1:], proj12, depth[0], gsim[0], gref, none),
+                         "bwd_src_ms": lambda: ops.warp_corr_backward(q4[0], q4[1:], proj12, depth[0], gsim[0], None, gsrc)}
+                for k, fn in parts.items():
+                    fn()
+                    r[k] = float(np.median([window(fn, args.reps) for _ in range(args.windows)]))
+            payload = (V - 1) * D * H * W * 4 * C * 4
+            r["bwd_src_atomic_bytes"] = payload
+            r["bwd_src_atomic_tb_per_s"] = payload / (r["bwd_src_ms"] * 1e-3) / 1e12
+            # ATen's grid_sample backward alone (all source views)
+            grids = [aten_grid(pairs, v, depth) for v in range(1, V)]
+            warped = [F.grid_sample(feats[v], grids[v - 1], mode="bilinear", padding_mode="zeros", align_corners=True) for v in range(1, V)]
+            gw = torch.randn_like(warped[0])
+
+            def grid_bwd():
+                for v in range(1, V):
+                    torch.autograd.grad(warped[v - 1], feats[v], gw, retain_graph=True)
+            grid_bwd()
+            r["aten_grid_bwd_ms"] = float(np.median([window(grid_bwd, args.reps) for _ in range(args.windows)]))
+            r["activation_estimate_mb"] = (V - 1) * (C + 2) * D * H * W * 4 / 2 ** 20   # the issue's arithmetic: warped + grid per view
+            del warped, gw, grids, gref, gsrc, q4
+            rows[name] = dict(C=C, D=D, H=H, W=W, **r)
+            print(f"# {recipe} {name}: fused {r['fused_ms']['median']:.3f} ms  aten {r['aten_ms']['median']:.3f} ms  "
+                  f"peak {r['fused_peak_mb']:.0f} / {r['aten_peak_mb']:.0f} MB", file=sys.stderr, flush=True)
+        tot = {k: sum(rw[k]["median"] for rw in rows.values()) for k in ("fused_ms", "aten_ms")}
+        tot.update({k: sum(rw[k] for rw in rows.values()) for k in ("bwd_src_ms", "bwd_ref_ms", "fwd_ms", "aten_grid_bwd_ms", "bwd_src_atomic_bytes")})
+        out["recipes"][recipe] = dict(views=V, passes=rows, per_sample=tot)
+    print(json.dumps(out))
+    if args.md:
+        with open(args.md, "w") as f:
+            f.write(markdown(out))
+
+
+def markdown(out):
+    lines = ["# Cost aggregation, forward + backward: fused (K1 + K1b) against ATen grid_sample", "",
+             f"`scripts/costagg_train_bench.py` on {out['device']}, one process, arms alternating; median of {out['windows']} windows of "
+             f"{out['reps']} repetitions, per sample (batch 1).  Times in ms, memory in MB (peak allocated over one forward + "
+             "backward, above what was allocated before).", ""]
+    for recipe, r in out["recipes"].items():
+        lines += [f"## {recipe} ({r['views']} views)", "",
+                  "| pass | C | D | H x W | fused fwd+bwd | ATen fwd+bwd | ATen / fused | K1 fwd | dRef kernel | dSrc kernel | ATen grid_sample bwd | dSrc atomics TB/s | fused peak | ATen peak |",
+                  "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+        for name, p in r["passes"].items():
+            lines.append(f"| {name} | {p['C']} | {p['D']} | {p['H']} x {p['W']} | {p['fused_ms']['median']:.3f} | {p['aten_ms']['median']:.3f} | "
+                         f"{p['aten_over_fused']:.2f} | {p['fwd_ms']:.3f} | {p['bwd_ref_ms']:.3f} | {p['bwd_src_ms']:.3f} | {p['aten_grid_bwd_ms']:.3f} | "
+                         f"{p['bwd_src_atomic_tb_per_s']:.2f} | {p['fused_peak_mb']:.0f} | {p['aten_peak_mb']:.0f} |")
+        t = r["per_sample"]
+        lines += ["", f"Per sample: fused {t['fused_ms']:.2f} ms, ATen {t['aten_ms']:.2f} ms ({t['aten_ms'] / t['fused_ms']:.2f}x); "
+                      f"dSrc kernels {t['bwd_src_ms']:.2f} ms for {t['bwd_src_atomic_bytes'] / 1e9:.2f} GB of atomic payload, "
+                      f"dRef kernels {t['bwd_ref_ms']:.2f} ms, ATen grid_sample backward {t['aten_grid_bwd_ms']:.2f} ms.", ""]
+    return "\n".join(lines)
+
+
+if __name__ == "__main__":
+    main()
