@@ -85,6 +85,8 @@ SIGNATURES = {
     "dmvs_prob_regress": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p]),
     "dmvs_depth_select": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "dmvs_depth_regress": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "dmvs_depth_regress_backward": (_i, [_p, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "dmvs_dual_depth_loss_backward": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
 }
 
 EINVAL, EUNSUPPORTED = -1, -2   # include/dmvs.h

@@ -208,3 +208,6 @@ extern "C" int dmvs_depth_select(const float* dsp_4hw, const float* interval, in
     depth_select_kernel<<<dim3(ceil_div(W, 256), H), 256, 0, (hipStream_t)stream>>>(dsp_4hw, interval, mode, H, W, sel, conf);
     DMVS_LAUNCH_CHECK();
 }
+
+// K4b: the backward of the regression (same translation unit: it repeats the forward's softmax in the forward's order)
+#include "depth_regress_bwd.h"

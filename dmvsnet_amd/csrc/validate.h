@@ -307,3 +307,142 @@ extern "C" int dmvs_dual_depth_loss(const float* dsp_main, const float* dsp_refi
     dual_depth_finish_kernel<<<1, VAL_WG, 0, (hipStream_t)stream>>>(f);
     DMVS_LAUNCH_CHECK();
 }
+
+// ------------------------------------------------------------------------------------------------------------------------ N6b
+// Backward of the loss part of dual_depth_loss_kernel: d total / d dsp_main, d total / d dsp_refine, written as a GATHER.  A thread
+// owns one pixel and collects its own terms (the four smooth-L1 depth terms, the two "variance" terms, in which var_gt depends on
+// the estimate too) and a quarter of the derivative of each of the up to four 2x2 cells the pixel is a corner of, each term divided
+// by the count the forward divided its sum by (n, n_cells: the forward's counts2).  The cell centres are recomputed in the forward's
+// order, (((nw + ne) + sw) + se) * 0.25; min / max go to the channel val_min / val_max returned.  One writer per element, a fixed
+// order of the four cells, no atomics: two runs give the same bits.  Masked pixels and cells are SELECTED out as in the forward: a
+// masked pixel gets exactly 0, a NaN under the mask reaches nothing, and a count of zero (empty mask: the forward's loss is NaN)
+// selects no term, so the gradient is all zeros, as autograd's is for the mean of nothing.
+struct ValBwdArgs {
+    const float* dsp[2];
+    const float* gt;
+    const float* mask;
+    const long long* counts2;   // n, n_cells of the forward
+    const float* g_total;       // [1] upstream gradient on the total
+    float* g_dsp[2];
+    int h, w;
+    float weight;
+};
+
+// d sl1(u) / du
+__device__ __forceinline__ float val_dsl1(float u) { return fabsf(u) < 1.f ? u : (u > 0.f ? 1.f : -1.f); }
+__device__ __forceinline__ float val_sgn(float u) { return u > 0.f ? 1.f : (u < 0.f ? -1.f : 0.f); }
+
+__global__ __launch_bounds__(256) void dual_depth_loss_bwd_kernel(const ValBwdArgs a) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= a.w) return;
+    const size_t HW = (size_t)a.h * a.w, pix = (size_t)y * a.w + x;
+    const float* gt_b = a.gt + b * HW;
+    const float* mask_b = a.mask + b * HW;
+    const double n = (double)a.counts2[0], nc = (double)a.counts2[1], gw = (double)a.g_total[0] * (double)a.weight;
+    // total = sum over the two outputs of 2 m0 + 2 m1 + m2 + m3 + m4..m7; m0, m1 are means over 2n, m2, m3 over n, m4..m7 over n_cells
+    const float kd = (float)(gw / n), kv = (float)(gw / n), kc = (float)(gw * 0.25 / nc);
+
+    // 3x3 neighbourhood: validity, ground truth, addresses (clamped: every load is in bounds)
+    bool nv[3][3];
+    float ng[3][3];
+    size_t np[3][3];
+    bool ncm[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int yy = y + i - 1, xx = x + j - 1;
+            const bool in = yy >= 0 && yy < a.h && xx >= 0 && xx < a.w;
+            const int yc = yy < 0 ? 0 : (yy < a.h ? yy : a.h - 1), xc = xx < 0 ? 0 : (xx < a.w ? xx : a.w - 1);
+            np[i][j] = (size_t)yc * a.w + xc;
+            nv[i][j] = in && mask_b[np[i][j]] > 0.5f;
+            ng[i][j] = gt_b[np[i][j]];
+            ncm[i][j] = ((xx ^ yy) & 1) == 0;   // row % 2 == col % 2
+        }
+    const bool valid = nv[1][1];
+    // the four cells the pixel is a corner of: cell (i, j) has the corners (i, j), (i, j + 1), (i + 1, j), (i + 1, j + 1)
+    bool cv[2][2];
+    float gbar[2][2];
+    bool anyc = false;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            cv[i][j] = nv[i][j] && nv[i][j + 1] && nv[i + 1][j] && nv[i + 1][j + 1];
+            gbar[i][j] = (((ng[i][j] + ng[i][j + 1]) + ng[i + 1][j]) + ng[i + 1][j + 1]) * 0.25f;
+            anyc = anyc || cv[i][j];
+        }
+    const float g = ng[1][1];
+
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        if (!a.g_dsp[s]) continue;
+        const float* dsp_b = a.dsp[s] + (size_t)b * 4 * HW;
+        float* out_b = a.g_dsp[s] + (size_t)b * 4 * HW;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {   // q = 0: channels 0, 1 ("small"); q = 1: channels 2, 3 ("huge")
+            const float* p0 = dsp_b + (size_t)(2 * q) * HW;
+            const float* p1 = p0 + HW;
+            const float d0 = p0[pix], d1 = p1[pix];
+            // depth terms: 2 * mean over 2n of sl1(d - g) * weight
+            float o0 = kd * val_dsl1(d0 - g), o1 = kd * val_dsl1(d1 - g);
+            // variance term: sl1(|d0 - d1| - var_gt), var_gt the larger of |d0 - g|, |d1 - g| (the forward's where)
+            const float a0 = fabsf(d0 - g), a1 = fabsf(d1 - g);
+            const bool far1 = a0 < a1;
+            const float du = kv * val_dsl1(fabsf(d0 - d1) - (far1 ? a1 : a0));
+            const float sd = val_sgn(d0 - d1);
+            o0 += du * (sd - (far1 ? 0.f : val_sgn(d0 - g)));
+            o1 += du * (-sd - (far1 ? val_sgn(d1 - g) : 0.f));
+            // cell centres: surfaces A = where(cm, min, max), B = where(~cm, min, max) of the pair
+            float A[3][3], Bs[3][3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float e0 = p0[np[i][j]], e1 = p1[np[i][j]];
+                    const float mn = val_min(e0, e1), mx = val_max(e0, e1);
+                    A[i][j] = ncm[i][j] ? mn : mx;
+                    Bs[i][j] = ncm[i][j] ? mx : mn;
+                }
+            float DA = 0.f, DB = 0.f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const float sa = (((A[i][j] + A[i][j + 1]) + A[i + 1][j]) + A[i + 1][j + 1]) * 0.25f;
+                    const float sb = (((Bs[i][j] + Bs[i][j + 1]) + Bs[i + 1][j]) + Bs[i + 1][j + 1]) * 0.25f;
+                    DA += cv[i][j] ? val_dsl1(sa - gbar[i][j]) : 0.f;
+                    DB += cv[i][j] ? val_dsl1(sb - gbar[i][j]) : 0.f;
+                }
+            const bool min0 = d0 < d1 || d0 != d0, max0 = d0 > d1 || d0 != d0;   // val_min / val_max returned channel 0
+            const float gmin = ncm[1][1] ? DA : DB, gmax = ncm[1][1] ? DB : DA;
+            const float c0 = kc * ((min0 ? gmin : 0.f) + (max0 ? gmax : 0.f));
+            const float c1 = kc * ((min0 ? 0.f : gmin) + (max0 ? 0.f : gmax));
+            o0 += anyc ? c0 : 0.f;
+            o1 += anyc ? c1 : 0.f;
+            out_b[(size_t)(2 * q) * HW + pix] = valid ? o0 : 0.f;
+            out_b[(size_t)(2 * q + 1) * HW + pix] = valid ? o1 : 0.f;
+        }
+    }
+}
+
+extern "C" int dmvs_dual_depth_loss_backward(const float* dsp_main, const float* dsp_refine, const float* gt, const float* mask,
+                                             int B, int h, int w, float weight, const long long* counts2, const float* g_total,
+                                             float* g_dsp_main, float* g_dsp_refine, dmvs_stream_t stream) {
+    if (!dsp_main || !dsp_refine || !gt || !mask || !counts2 || !g_total || !val_dims_ok(B, h, w)) return DMVS_EINVAL;
+    if (!g_dsp_main && !g_dsp_refine) return DMVS_EINVAL;
+    ValBwdArgs a;
+    a.dsp[0] = dsp_main;
+    a.dsp[1] = dsp_refine;
+    a.gt = gt;
+    a.mask = mask;
+    a.counts2 = counts2;
+    a.g_total = g_total;
+    a.g_dsp[0] = g_dsp_main;
+    a.g_dsp[1] = g_dsp_refine;
+    a.h = h;
+    a.w = w;
+    a.weight = weight;
+    dual_depth_loss_bwd_kernel<<<dim3(ceil_div(w, 256), h, B), 256, 0, (hipStream_t)stream>>>(a);
+    DMVS_LAUNCH_CHECK();
+}

@@ -817,3 +817,54 @@ def depth_regress(logits: torch.Tensor, depth_dhw: torch.Tensor, interval: torch
         hyp = H * W if affine else D * H * W
         timer.end("depth_regress", t0, 0.0, 4.0 * (4 * D * H * W + hyp + (9 if mode == 0 else 6) * H * W + (4 * D * H * W if want_prob else 0)))
     return dsp, sel, conf, prob
+
+
+def depth_regress_backward(logits: torch.Tensor, hyp_dhw: torch.Tensor, alpha: float, mode: int, dsp: torch.Tensor,
+                           g_dsp: Optional[torch.Tensor], g_sel: Optional[torch.Tensor], want_hyp: bool,
+                           g_logits: Optional[torch.Tensor] = None, g_hyp: Optional[torch.Tensor] = None):
+    """K4b.  logits [4,D,H,W], hyp [D,H,W], dsp [4,H,W] (the forward's), g_dsp [4,H,W] | None, g_sel ([4,H,W] mode 0 | [H,W] mode 1)
+    | None -> (g_logits [4,D,H,W], g_hyp [D,H,W] | None).  ``g_logits`` / ``g_hyp``: buffers to write into (fully overwritten)."""
+    _req(logits, hyp_dhw, dsp, g_dsp, g_sel, g_logits, g_hyp)
+    _, D, H, W = logits.shape
+    assert logits.shape[0] == 4 and tuple(hyp_dhw.shape) == (D, H, W) and tuple(dsp.shape) == (4, H, W)
+    assert g_dsp is None or tuple(g_dsp.shape) == (4, H, W)
+    assert g_sel is None or tuple(g_sel.shape) == ((4, H, W) if mode == 0 else (H, W))
+    if g_dsp is None and g_sel is None:
+        raise _lib.DmvsError("depth_regress_backward: no upstream gradient (g_dsp and g_sel are both None)")
+    if g_logits is None:
+        g_logits = torch.empty_like(logits)
+    if want_hyp and g_hyp is None:
+        g_hyp = torch.empty_like(hyp_dhw)
+    assert g_logits.shape == logits.shape and (g_hyp is None or g_hyp.shape == hyp_dhw.shape)
+    t0 = timer.begin() if timer is not None else None
+    code = _lib.load().dmvs_depth_regress_backward(_ptr(logits), _ptr(hyp_dhw), float(alpha), mode, D, H, W, _ptr(dsp), _ptr(g_dsp),
+                                                   _ptr(g_sel), _ptr(g_logits), _ptr(g_hyp if want_hyp else None), _stream())
+    if code:
+        if t0 is not None:
+            timer.cancel(t0)
+        _lib.check(code, "dmvs_depth_regress_backward")
+    _log("depth_regress")
+    if t0 is not None:
+        # algorithmic bytes: the logit volume read and its gradient written once (32 N, N = D H W), the hypotheses read (and their
+        # gradient written), dsp and the upstream planes
+        planes = 4 + (4 if g_dsp is not None else 0) + (0 if g_sel is None else (4 if mode == 0 else 1))
+        timer.end("depth_regress", t0, 0.0, 4.0 * (8 * D * H * W + (2 if want_hyp else 1) * D * H * W + planes * H * W))
+    return g_logits, (g_hyp if want_hyp else None)
+
+
+def dual_depth_loss_backward(dsp_main: torch.Tensor, dsp_refine: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, weight: float,
+                             counts: torch.Tensor, g_total: torch.Tensor, want_main: bool = True, want_refine: bool = True):
+    """N6b.  dsp_* [B,4,h,w], gt / mask [B,h,w] fp32, ``counts`` [2] int64 (n, n_cells: the forward's), ``g_total`` [1] fp32 on the
+    device -> (g_dsp_main, g_dsp_refine), None where not wanted.  Not logged as a launch family (as the N6 forward)."""
+    _req(dsp_main, dsp_refine, gt, mask, g_total)
+    B, h, w = gt.shape
+    assert tuple(dsp_main.shape) == tuple(dsp_refine.shape) == (B, 4, h, w) and mask.shape == gt.shape
+    assert counts.dtype == torch.int64 and counts.is_cuda and counts.numel() == 2 and g_total.numel() == 1
+    g_main = torch.empty_like(dsp_main) if want_main else None
+    g_refine = torch.empty_like(dsp_refine) if want_refine else None
+    if g_main is None and g_refine is None:
+        return None, None
+    _lib.check(_lib.load().dmvs_dual_depth_loss_backward(_ptr(dsp_main), _ptr(dsp_refine), _ptr(gt), _ptr(mask), B, h, w, float(weight),
+                                                         _ptr(counts), _ptr(g_total), _ptr(g_main), _ptr(g_refine), _stream()),
+               "dmvs_dual_depth_loss_backward")
+    return g_main, g_refine

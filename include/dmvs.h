@@ -366,6 +366,23 @@ int dmvs_depth_regress_affine(const float* logits_4dhw, const float* base_hw, co
                               float alpha, int mode, int D, int H, int W, float* dsp_4hw, float* sel,
                               float* conf_hw, float* prob_4dhw, dmvs_stream_t stream);
 
+/* K4b: backward of dmvs_depth_regress (csrc/depth_regress_bwd.h; host side dmvsnet_amd/head.py).  The softmax is recomputed from the
+ * logits in the forward's operation order (nothing but logits, hypotheses and dsp is kept from the forward), and min / max route to
+ * the channel the forward selected, read off the forward's dsp_4hw.
+ *   logits_4dhw, hyp_dhw, alpha, mode, D, H, W   as the forward call (hypotheses as a volume; the affine form has no backward)
+ *   dsp_4hw      [4][H][W] the forward's expectations E
+ *   g_dsp_4hw    [4][H][W] upstream gradient on depth_sub_plus, or NULL
+ *   g_sel        upstream gradient on the selection -- mode 0: [4][H][W] (depth_values_c), mode 1: [H][W] (depth) -- or NULL;
+ *                at least one of g_dsp_4hw, g_sel is required.  G[c] = g_dsp[c] + what g_sel sends to channel c through the eight
+ *                (mode 0, mvsnet.py:33-56) or four (mode 1, mvsnet.py:80-91) checkerboard cases and (min, max) of the pair.
+ *   g_logits_4dhw [4][D][H][W] out: alpha * p[c][d] * (hyp[d] - E[c]) * G[c], p = softmax_d(alpha * logits[c])
+ *   g_hyp_dhw    [D][H][W] out or NULL: ((p[0][d] G[0] + p[1][d] G[1]) + p[2][d] G[2]) + p[3][d] G[3]
+ * The confidence is computed under no_grad in the reference and has no gradient.  Plain stores, one writer per element: bitwise
+ * reproducible.  1 <= D <= 64, above: DMVS_EUNSUPPORTED; any H, W. */
+int dmvs_depth_regress_backward(const float* logits_4dhw, const float* hyp_dhw, float alpha, int mode, int D, int H, int W,
+                                const float* dsp_4hw, const float* g_dsp_4hw, const float* g_sel, float* g_logits_4dhw,
+                                float* g_hyp_dhw, dmvs_stream_t stream);
+
 /* N4: geometric-consistency check of one (reference, source) depth-map pair -- the inner step of the fusion
  * filter.  Replaces reproject_with_depth_pytorch + check_geometric_consistency (filter/pcd.py:151-242).
  *   depth_ref, depth_src [H][W]; proj33: 33 floats folded on the host from the two cameras:
@@ -476,6 +493,19 @@ long dmvs_dual_depth_loss_workspace(int B, int h, int w);
 int dmvs_dual_depth_loss(const float* dsp_main, const float* dsp_refine, const float* gt, const float* mask, const float* depth,
                          int B, int h, int w, float weight, const float* thres3, double* workspace, float* total_loss,
                          float* terms16, long long* counts2, double* image_sums, float* metrics4, dmvs_stream_t stream);
+
+/* N6b: backward of the loss of dmvs_dual_depth_loss: g_dsp_* = g_total[0] * d total_loss / d dsp_*, every term as the forward defines
+ * it (the doubled smooth-L1 depth terms; the two "variance" terms, through both arguments: var_gt depends on the estimate; the four
+ * cell-centre terms with exact quarter weights over the cells whose four corners are valid).  A gather: a pixel collects its own
+ * terms and a quarter of each of the up to four cells it is a corner of, each divided by the forward's count.
+ *   dsp_main, dsp_refine, gt, mask, B, h, w, weight   as the forward call
+ *   counts2 [2] i64 (device): n, n_cells as the forward wrote them;  g_total [1] (device): upstream gradient on the total
+ *   g_dsp_main, g_dsp_refine [B][4][h][w] out, one of them may be NULL (skipped); fully overwritten.
+ * Masked pixels get exactly 0 (selected, never multiplied): NaN under the mask does not leak; with an empty mask (forward: NaN) the
+ * gradient is all zeros.  No atomics: bitwise reproducible. */
+int dmvs_dual_depth_loss_backward(const float* dsp_main, const float* dsp_refine, const float* gt, const float* mask, int B, int h,
+                                  int w, float weight, const long long* counts2, const float* g_total, float* g_dsp_main,
+                                  float* g_dsp_refine, dmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
