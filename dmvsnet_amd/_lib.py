@@ -27,6 +27,7 @@ SIGNATURES = {
     "dmvs_version": (_i, []),
     "dmvs_error_string": (ctypes.c_char_p, [_i]),
     "dmvs_tune": (_i, [ctypes.c_char_p, _i]),
+    "dmvs_zpad_live_mask": (ctypes.c_long, [_i, _i, _i, _i]),
     "dmvs_nchw_to_hwc": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "dmvs_planar_to_hwc": (_i, [_p, ctypes.c_long, _i, _i, _i, _i, _p, _p]),
     "dmvs_image_ingest": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p]),

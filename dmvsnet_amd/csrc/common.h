@@ -37,6 +37,47 @@ static inline double wino_filter(const double g[9], int i, int p) {
     return u;
 }
 
+// Zero-padding depth taps (dmvs_tune("zpad_skip")).  A 3x3x3 layer on a shallow volume multiplies whole planes of zero
+// padding: on depth D, 2 of the 3 * D (output plane, depth tap) pairs of a stride-1 layer, 1 of 3 * D/2 of a stride-2 layer
+// and 1 of 3 * D of a transposed one.  These products are exact zeros, so a kernel may leave them out (the live products keep
+// their order: the result is value-equal for finite inputs).  zpad_live_mask is the ONE statement of which pairs are live;
+// every skipping kernel derives its skip from it: per tile (K3w) or per unit (K3r) in scalar registers, or once on the host where
+// the whole launch has the same dead taps (K3 on volumes of one output / input plane).  Skipping pays only where every wave that
+// meets at a barrier skips the same work: a form in which only some waves of a workgroup skip was measured and dropped (K3's
+// two-plane tiles, the `prob` head: docs/kernels/K3_conv_mfma.md, K2_prob_and_direct.md).
+//   bit 3 * p + kz: plane p of the tile (p in [0, TZ), plane oz0 + p of the volume) takes a non-padding plane through tap kz
+//   DMVS_ZFORM_S1: stride 1, pad 1; planes are OUTPUT planes of a depth-D volume, tap kz reads input plane z + kz - 1
+//   DMVS_ZFORM_S2: stride 2, pad 1; planes are OUTPUT planes z < (D + 1) / 2, tap kz reads input plane 2 z + kz - 1 of D
+//   DMVS_ZFORM_T2: transposed, stride 2, pad 1, output_padding 1 in the kernels' GATHER form on the input grid: planes are
+//                  INPUT planes z < D; taps 1 and 2 (output planes 2 z and 2 z + 1) read plane z, tap 0 (output plane
+//                  2 z + 1) reads plane z + 1 -- the scatter view's dead pair (input plane 0, tap 0 -> output plane -1) never
+//                  appears in this form, the dead one is (plane D - 1, tap 0), which reads the padding plane D.
+// A plane of the tile past the end of the volume has no live tap.  TZ <= 10.
+enum { DMVS_ZFORM_S1 = 0, DMVS_ZFORM_S2 = 1, DMVS_ZFORM_T2 = 2 };
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+constexpr unsigned zpad_live_mask(int form, int D, int oz0, int TZ) {
+    unsigned m = 0;
+    for (int p = 0; p < TZ; ++p) {
+        const int z = oz0 + p;
+        const int nplanes = form == DMVS_ZFORM_S2 ? (D + 1) / 2 : D;
+        if (z < 0 || z >= nplanes) continue;
+        for (int kz = 0; kz < 3; ++kz) {
+            const int iz = form == DMVS_ZFORM_S1 ? z + kz - 1 : form == DMVS_ZFORM_S2 ? 2 * z + kz - 1 : (kz == 0 ? z + 1 : z);
+            if (iz >= 0 && iz < D) m |= 1u << (3 * p + kz);
+        }
+    }
+    return m;
+}
+
+// launches on input volumes up to this depth take the skipping instantiations.  From the layer table (config 2, one layer alone):
+// depth 2 -14 .. -16 % (K3r conv4, K3w conv2), depth 4 -5 % (K3w) and -2 % (K3r), depth 8 +1 % (K3r conv4: 8 % dead pairs do
+// not pay for the per-unit choice of a code copy) -- and deeper volumes must keep exactly the code they had.
+constexpr int kZpadMaxDepth = 4;
+extern long g_zpad_skip;   // layout.hip, dmvs_tune("zpad_skip")
+static inline bool zpad_skip_wanted(int D) { return g_zpad_skip && D <= kZpadMaxDepth; }
+
 #ifdef __HIPCC__
 __device__ __forceinline__ bool xcd_tile(int nx, int ny, int nz, bool z_fast, int& bx, int& by, int& bz) {
     const int n = nx * ny * nz, per = (n + 7) >> 3;

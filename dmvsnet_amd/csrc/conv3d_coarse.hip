@@ -103,8 +103,19 @@ struct CoarseGeom {
     static_assert(LDS <= 160 * 1024, "ring + exchange must fit the LDS");
 };
 
+// ZSKIP (dmvs_tune("zpad_skip"), 3D layers on shallow volumes): a unit is ONE output plane, so on the first
+// plane depth tap 0 and on the last plane depth tap 2 multiply a plane of zero padding (zpad_live_mask, common.h) for the whole
+// workgroup: those (k-group, depth tap) steps keep their place in the stage -- the finish of the previous unit and the tile loads
+// issued between the steps stay exactly where they are, every stage still issues its NS loads per wave -- but lose their patch
+// reads, the input transform row and their 4 NCB MFMAs.  The step loop of a stage is compiled once per set of dead taps (none,
+// tap 0, tap 2, both) as straight-line code and picked per unit with scalar compares.
+// ZSKIP is a parameter of the enclosing struct, not of the kernel: both forms are `coarse_kernel<KD, CIN, NCB, V4>` to the static
+// check of the ring's load counts (tests/test_static_isa.py), which so covers the skipping form too.
+template <bool ZSKIP>
+struct Coarse {
 template <int KD, int CIN, int NCB, bool V4>
-__global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
+static __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
+    static_assert(!ZSKIP || KD == 3, "only the 3D layers have depth taps");
     typedef CoarseGeom<KD, CIN, NCB, V4> G;
     constexpr int NST = G::NST, GPH = G::GPH, RING = G::RING, IXP = G::IXP, PS = G::PS, PF = G::PF, NS = G::NS, LW = G::LW;
     constexpr unsigned kInvalid = kWinoInvalid;
@@ -270,6 +281,11 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
     for (int j = 0; j < nunits; ++j) {
         int ox0, oy0, oz;
         coords(j, ox0, oy0, oz);
+        int zsel = 0;   // ZSKIP: bit 0 = depth tap 0, bit 1 = depth tap 2 of this unit's plane meets only zero padding (scalar)
+        if constexpr (ZSKIP) {
+            const unsigned dead = ~zpad_live_mask(DMVS_ZFORM_S1, a.D, oz, 1);
+            zsel = (int)((dead & 1u) | ((dead >> 1) & 2u));
+        }
         acc4_t acc[NCB][4];
 #pragma unroll
         for (int nb = 0; nb < NCB; ++nb)
@@ -298,9 +314,13 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
             const float* pb = smem + ring_c * G::STAGE_F + baseB;
             ring_c = ring_c + 1 == RING ? 0 : ring_c + 1;
 #pragma unroll
+            for (int zc = 0; zc < (ZSKIP ? 4 : 1); ++zc) {   // ZSKIP: one copy of the step loop per set of dead taps
+            if (ZSKIP && zc != zsel) continue;
+#pragma unroll
             for (int st = 0; st < NSTEP; ++st) {
                 const int gg = st / KD, kz = st - gg * KD;
                 const int o = gg * 4 * PS + kz * G::PLANE;
+                if (!ZSKIP || !((kz == 0 && (zc & 1)) || (kz == 2 && (zc & 2)))) {
                 float2_t rd[6];
                 wino_read_pairs(pa + o, rd);
                 wino_read_pairs(pb + o, rd + 3);
@@ -314,10 +334,13 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
                     acc[nb][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[2], wv.z, acc[nb][2], 0, 0, 0);
                     acc[nb][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[3], wv.w, acc[nb][3], 0, 0, 0);
                 }
+                }
                 if (st == FIN_AT && fin_now) finish_store(pox, poy, poz);
 #pragma unroll
                 for (int sl = 0; sl < NS; ++sl)
                     if (sl * NSTEP / NS == st) issue_slot(sl);
+            }
+            if (ZSKIP) break;   // (exactly one copy runs: also what the static load count of the ring sees)
             }
 #ifdef DMVS_K3R_TRACE
             asm volatile("s_nop 0" ::: "memory");
@@ -352,6 +375,8 @@ __global__ __launch_bounds__(512, 2) void coarse_kernel(CoarseArgs a) {
 #endif
 }
 
+};
+
 struct RCfg { int cin, cout, kd, ncb; };
 // the layers this kernel is compiled for; ncb = 16-channel output blocks per workgroup (Cout / (16 ncb) cout groups)
 const RCfg kRCfgs[] = {
@@ -370,7 +395,11 @@ int nw_of(const RCfg& c) { return (c.cin / 8) * c.kd * c.ncb; }   // NST * GPH =
 template <int KD, int CIN, int NCB, bool V4>
 int launch_coarse(CoarseArgs a, hipStream_t st) {
     typedef CoarseGeom<KD, CIN, NCB, V4> G;
-    auto kernel = coarse_kernel<KD, CIN, NCB, V4>;
+    auto kernel = Coarse<false>::coarse_kernel<KD, CIN, NCB, V4>;
+    // shallow volumes: skip the padding planes' steps.  16-byte loader only: the dword loader's form is at the register limit (256) with
+    // the copies, and the compiler then lays out the stage wait in a way the static load count cannot follow
+    if constexpr (KD == 3 && V4)
+        if (zpad_skip_wanted(a.D)) kernel = Coarse<true>::coarse_kernel<KD, CIN, NCB, V4>;
     // a device that cannot give the kernel its ring + exchange (<= 160 KB on gfx950, with no headroom for the 64 -> 64 2D form) is
     // "shape not covered here", not a hard error: `auto` then falls back to K3w
     if (dmvs_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), G::LDS)) { (void)hipGetLastError(); return DMVS_EUNSUPPORTED; }

@@ -176,8 +176,15 @@ struct ConvGeom {
 // two 32-channel blocks each, so a workgroup owns half as many rows and the layer yields twice as many workgroups of
 // half the MFMA work -- the 1/8-scale bottleneck layers (conv5 / conv6: a few hundred workgroups for 1024 SIMDs)
 // otherwise leave most of the chip idle in their last round.
-template <int M, int MB, int STRIDE, int KD, int KS, int CI_CH, int TZ, int TY, int ROWS, bool V4, bool MBS = false>
+// ZDEAD (dmvs_tune("zpad_skip"), 3x3x3 layers on shallow volumes): bit kz set = depth tap kz meets only zero padding for every
+// output plane of the launch (zpad_live_mask, common.h; the host picks the instantiation).  Its 9 * GPC k-steps are left out, or
+// the packed-K steps all of whose taps are dead (conv1: taps 0-7 go, tap 8 shares its step with kz = 1 and stays).  Weights are
+// not re-packed and the live products keep their order; the tile and weight loads are untouched.  Compiled for ZDEAD = 1 on the
+// flat tile (a stride-2 layer taking 2 planes to 1: tap 0 reads plane -1).  ZDEAD = 0 is instruction for instruction the kernel
+// as it was before the parameter existed.
+template <int M, int MB, int STRIDE, int KD, int KS, int CI_CH, int TZ, int TY, int ROWS, bool V4, bool MBS = false, unsigned ZDEAD = 0>
 __global__ __launch_bounds__(256, (M == 16 ? 3 : 1)) void conv_mfma_kernel(ConvArgs a) {
+    static_assert(!ZDEAD || (KD == 3 && KS == 3), "only the 3x3x3 layers have depth taps");
     typedef Frag<M> F;
     typedef typename F::acc_t acc_t;
     typedef ConvGeom<M, STRIDE, KD, KS, CI_CH, TZ, TY, V4> G;
@@ -314,6 +321,13 @@ __global__ __launch_bounds__(256, (M == 16 ? 3 : 1)) void conv_mfma_kernel(ConvA
             // the loop cost 1.6 VALU instructions per MFMA -- paid in full next to fp32 MFMAs)
 #pragma unroll
             for (int st = 0; st < G::NSTEPS; ++st) {
+                if (ZDEAD) {   // the step's taps st * TPG .. (the padded ones carry zero weights) span the depth taps kz0 .. kz1
+                    const int kz0 = st * G::TPG / (KS * KS), kz1 = min(st * G::TPG + G::TPG - 1, G::NT - 1) / (KS * KS);
+                    bool dead = true;
+#pragma unroll
+                    for (int kz = kz0; kz <= kz1; ++kz) dead = dead && ((ZDEAD >> kz) & 1);
+                    if (dead) continue;
+                }
                 float av[MBL];
 #pragma unroll
                 for (int mb = 0; mb < MBL; ++mb) av[mb] = wl[(st * MB + mb0 + mb) * 64];
@@ -337,6 +351,7 @@ __global__ __launch_bounds__(256, (M == 16 ? 3 : 1)) void conv_mfma_kernel(ConvA
             for (int ky = 0; ky < KS; ++ky)
 #pragma unroll
                 for (int kx = 0; kx < KS; ++kx) {
+                    if (ZDEAD && ((ZDEAD >> kz) & 1)) continue;
                     const int toff = (kz * IY + ky) * IXP + kx;
                     const int t = (kz * KS + ky) * KS + kx;
 #pragma unroll
@@ -548,8 +563,12 @@ struct DeconvGeom {
 // SIMD -- conv7 only ever runs on the 1/8-scale grids of 74-520 workgroups, where the 32-row form left most SIMDs with one
 // wave or none (r04 layer table: 3.6-4.8x its floor; 0.62 -> 0.51 ms per depth map, +0.4 % end to end).  Choosing the block
 // by WORKGROUP instead (four rows, half the weight bytes per workgroup) measured 0.49 ms alone but 89.7 vs 90.5 end to end.
-template <int M, int KD, int CI_CH, int TZ, int TY, bool PYM, bool PREF, int NCH = 0, int NMB = 1>
+// ZSKIP (dmvs_tune("zpad_skip"), a volume of ONE input plane; the host picks the instantiation): input offset oz = 1 is the padding
+// plane D (depth tap 0 of the odd output plane: zpad_live_mask's transposed form) for every wave; that block -- 4 (oy, ox) offsets x
+// GPC k-groups, a third of the k-steps -- is left out.  The loads (and with them PREF's counted wait) are untouched.
+template <int M, int KD, int CI_CH, int TZ, int TY, bool PYM, bool PREF, int NCH = 0, int NMB = 1, bool ZSKIP = false>
 __global__ __launch_bounds__(256, (M == 16 ? 3 : 1)) void deconv_mfma_kernel(ConvArgs a) {
+    static_assert(!ZSKIP || (KD == 3 && TZ == 1), "the flat tile of a 3x3x3 layer");
     typedef Frag<M> F;
     typedef typename F::acc_t acc_t;
     typedef DeconvGeom<M, KD, CI_CH, TZ, TY, PYM, NMB> G;
@@ -696,6 +715,7 @@ __global__ __launch_bounds__(256, (M == 16 ? 3 : 1)) void deconv_mfma_kernel(Con
                 for (int ox = 0; ox < 2; ++ox)
 #pragma unroll
                     for (int g = 0; g < GPC; ++g) {
+                        if (ZSKIP && oz == 1) continue;   // (the last block: no later step number depends on it)
                         float bv[XB];
 #pragma unroll
                         for (int xb = 0; xb < XB; ++xb)
@@ -846,8 +866,15 @@ int launch_with_lds(K kernel, dim3 tiles, size_t lds_bytes, ConvArgs a, hipStrea
     DMVS_LAUNCH_CHECK();
 }
 
-template <int M, int MB, int STRIDE, int KD, int KS, int CI_CH, int TZ, int TY, bool V4, bool MBS = false>
+template <int M, int MB, int STRIDE, int KD, int KS, int CI_CH, int TZ, int TY, bool V4, bool MBS = false, unsigned ZDEAD = 0>
 int launch_conv_tile_v(const ConvArgs& a, hipStream_t st) {
+    // shallow volumes: the instantiation that skips zero-padding depth taps.  Only for the FLAT tile (TZ = 1: the output has one
+    // plane, every wave of every workgroup has the same dead taps, known here) of a stride-2 layer taking 2 planes to 1.  With two
+    // planes per tile the waves of the first plane would skip and those of the second not; they meet at the chunk barrier and sit
+    // on different SIMDs, so the workgroup is no faster (measured, docs/kernels/K3_conv_mfma.md).  16-byte tile loads only.
+    if constexpr (KD == 3 && KS == 3 && STRIDE == 2 && TZ == 1 && V4 && ZDEAD == 0)
+        if (zpad_skip_wanted(a.D) && a.Do == 1 && (~zpad_live_mask(DMVS_ZFORM_S2, a.D, 0, 1) & 7u) == 1u)
+            return launch_conv_tile_v<M, MB, STRIDE, KD, KS, CI_CH, TZ, TY, V4, MBS, 1u>(a, st);
     typedef ConvGeom<M, STRIDE, KD, KS, CI_CH, TZ, TY, V4> G;
     constexpr int ROWS = TZ * TY / (MBS ? 2 : 4);
     constexpr size_t lds2 = 2 * (size_t)(G::TILE_F + G::NSTEPS * MB * 64) * sizeof(float);
@@ -861,7 +888,7 @@ int launch_conv_tile_v(const ConvArgs& a, hipStream_t st) {
     ConvArgs b = a;
     dim3 grid(ceil_div(a.Wo, 32), ceil_div(a.Ho, TY), ceil_div(a.Do, TZ));
     b.single_buf = (KD == 3 && (long)grid.x * grid.y * grid.z >= g_single_buf_min_blocks) ? 1 : 0;
-    return launch_with_lds(conv_mfma_kernel<M, MB, STRIDE, KD, KS, CI_CH, TZ, TY, ROWS, V4, MBS>, grid, b.single_buf ? lds2 / 2 : lds2, b, st);
+    return launch_with_lds(conv_mfma_kernel<M, MB, STRIDE, KD, KS, CI_CH, TZ, TY, ROWS, V4, MBS, ZDEAD>, grid, b.single_buf ? lds2 / 2 : lds2, b, st);
 }
 
 // 16-byte tile loads need whole pieces inside a row and aligned rows
@@ -922,9 +949,17 @@ int launch_deconv_tile(const ConvArgs& a, hipStream_t st) {
     static_assert(lds <= 160 * 1024, "two pipeline stages must fit the 160 KB LDS");
     dim3 grid(ceil_div(a.W, 32), ceil_div(a.H, TY), ceil_div(a.D, TZ));
     // residual prefetch: conv11; conv9's 64 and conv7's 128 residual registers spill under the occupancy bound
+    // a volume of one input plane: skip the padding plane's k-steps (every wave reads it).  With two planes per tile only half of the
+    // waves would skip and the workgroup waits for the others (measured: no gain, docs/kernels/K3_conv_mfma.md)
+    const bool zskip = KD == 3 && TZ == 1 && zpad_skip_wanted(a.D) && a.D == 1 && !(zpad_live_mask(DMVS_ZFORM_T2, a.D, 0, 1) & 1u);
     if constexpr (PYM)   // conv11 (16 -> 8): 4 chunks, 4 residual groups of 4 loads = 32 registers
-        if (a.skip && g_deconv_prefetch && a.Cin == 4 * CI_CH)
+        if (a.skip && g_deconv_prefetch && a.Cin == 4 * CI_CH) {
+            if constexpr (KD == 3 && TZ == 1)
+                if (zskip) return launch_with_lds(deconv_mfma_kernel<M, KD, CI_CH, TZ, TY, PYM, true, 4, 1, true>, grid, lds, a, st);
             return launch_with_lds(deconv_mfma_kernel<M, KD, CI_CH, TZ, TY, PYM, true, 4>, grid, lds, a, st);
+        }
+    if constexpr (KD == 3 && TZ == 1)
+        if (zskip) return launch_with_lds(deconv_mfma_kernel<M, KD, CI_CH, TZ, TY, PYM, false, 0, NMB, true>, grid, lds, a, st);
     return launch_with_lds(deconv_mfma_kernel<M, KD, CI_CH, TZ, TY, PYM, false, 0, NMB>, grid, lds, a, st);
 }
 

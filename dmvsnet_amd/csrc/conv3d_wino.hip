@@ -97,8 +97,23 @@ __device__ __forceinline__ void load_rows64(__amdgpu_buffer_rsrc_t rs_w, float* 
 // Q4: the output is written as two quad-planar halves [half][D][Cout/8][H][W][4] (DMVS_OUT_Q4, the layout K1 samples).
 //     The MFMA operands are swapped (output channels = rows, tiles = columns), so a lane's 4 accumulator registers are 4
 //     CONSECUTIVE channels of ONE tile: a 16-byte piece per output pixel.
-template <int KD, int MB, int MBW, int TZ, int TRW, int GPC, bool Q4 = false>
+//
+// ZSKIP (dmvs_tune("zpad_skip"), shallow volumes): an input plane of the tile that is zero padding (or feeds only output planes
+//     past the volume's end) is skipped as a whole -- patch reads, B^T d B and its MFMA blocks -- and a live plane runs the
+//     MFMA blocks of its live (output plane, depth tap) pairs only (zpad_live_mask, common.h).  Which pairs are live depends on
+//     the tile alone (first planes: oz0 == 0; last planes: D - oz0), so the chunk body is compiled ONCE PER CASE as straight-line
+//     code and a tile picks its copy with scalar compares: no branch inside a body, the compiler keeps its interleaving.  The
+//     live products keep their order.  The tile loads are left as they are (a load instruction moves rows of two planes).
+//     Without ZSKIP the kernel is instruction for instruction what it was before the parameter existed.
+// the live pairs of tile case zc = (oz0 == 0) | (min(D - oz0, TZ + 1) - 1) << 1
+template <int TZ>
+__device__ __forceinline__ constexpr unsigned wino_zcase_live(int zc) {
+    return zpad_live_mask(DMVS_ZFORM_S1, (zc & 1) ? (zc >> 1) + 1 : TZ + (zc >> 1) + 1, (zc & 1) ? 0 : TZ, TZ);
+}
+
+template <int KD, int MB, int MBW, int TZ, int TRW, int GPC, bool Q4 = false, bool ZSKIP = false>
 __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
+    static_assert(!ZSKIP || KD == 3, "only the 3D layers have depth taps");
     typedef WinoGeom<KD, MB, MBW, TZ, TRW, GPC> G;
     constexpr int IY = G::IY, IZ = G::IZ, IXP = G::IXP, PS = G::PS, NTR = G::NTR;
     constexpr unsigned kInvalid = kWinoInvalid;
@@ -192,12 +207,24 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
             }
             const float* tile = curb + pbase;
             const float* wl = curb + G::TILE_F + lane * 4;
+            // ZSKIP: one copy of the chunk's MFMAs per tile case, LIVE = the case's live (output plane, depth tap) pairs, bit 3 * oz + kz
+            const int zsel = ZSKIP ? (oz0 == 0 ? 1 : 0) | (min(a.D - oz0, TZ + 1) - 1) << 1 : 0;   // scalar
+#pragma unroll
+            for (int zc = 0; zc < (ZSKIP ? 2 * (TZ + 1) : 1); ++zc) {
+            if (ZSKIP && zc != zsel) continue;
+            const unsigned LIVE = ZSKIP ? wino_zcase_live<TZ>(zc) : ~0u;
 #pragma unroll
             for (int g = 0; g < GPC; ++g)
 #pragma unroll
                 for (int pz = 0; pz < IZ; ++pz)
 #pragma unroll
                     for (int t = 0; t < TRW; ++t) {
+                        if constexpr (ZSKIP) {
+                            bool any = false;
+#pragma unroll
+                            for (int oz = 0; oz < TZ; ++oz) any |= pz - oz >= 0 && pz - oz <= 2 && ((LIVE >> (3 * oz + pz - oz)) & 1);
+                            if (!any) continue;
+                        }
                         const float* p = tile + g * 4 * PS + (pz * IY + 2 * t) * IXP;
                         float d[4][4];
                         if (DMVS_WKO & 8) {
@@ -217,6 +244,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
                         for (int oz = 0; oz < TZ; ++oz) {
                             const int kz = KD == 3 ? pz - oz : 0;
                             if (KD == 3 ? (kz < 0 || kz > 2) : (pz != oz)) continue;
+                            if (ZSKIP && !((LIVE >> (3 * oz + kz)) & 1)) continue;
 #pragma unroll
                             for (int mb = 0; mb < MBW; ++mb) {
                                 const float* wq = wl + (((kz * GPC + g) * MB + mg * MBW + mb) * 4) * 256;
@@ -232,6 +260,8 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(WinoArgs a) {
                             }
                         }
                     }
+            if (ZSKIP) break;
+            }
             if (a.single_buf && (!last || has_next)) {  // single stage: refill it once every wave is done with step k
                 if (!(DMVS_WKO & 32)) __syncthreads();
                 if (!last) stage(cur, c + 1, k + 1, smem);
@@ -668,8 +698,10 @@ long g_wino_persistent = 1;
 long g_wino_conv0_grid = 512;   // persistent workgroups of conv0_wino_kernel (dmvs_tune("wino_conv0_grid"), multiple of 8)
 namespace {
 
-template <int KD, int MB, int MBW, int TZ, int TRW, int GPC, bool Q4 = false>
+template <int KD, int MB, int MBW, int TZ, int TRW, int GPC, bool Q4 = false, bool ZSKIP = false>
 int launch_wino(WinoArgs a, bool single_buf, hipStream_t st) {
+    if constexpr (KD == 3 && TZ == 2 && !ZSKIP)   // conv2: the skipping instantiation on shallow volumes (deep ones: exactly this one)
+        if (zpad_skip_wanted(a.D)) return launch_wino<KD, MB, MBW, TZ, TRW, GPC, Q4, true>(a, single_buf, st);
     typedef WinoGeom<KD, MB, MBW, TZ, TRW, GPC> G;
     constexpr size_t lds2 = 2 * (size_t)G::BUF_F * sizeof(float);
     static_assert(lds2 / 2 <= 160 * 1024, "one stage must fit the LDS");
@@ -677,7 +709,7 @@ int launch_wino(WinoArgs a, bool single_buf, hipStream_t st) {
     if (g_wino_stages) single_buf = g_wino_stages == 1;
     a.single_buf = (single_buf || lds2 > 160 * 1024) ? 1 : 0;
     const size_t lds = a.single_buf ? lds2 / 2 : lds2;
-    auto kernel = conv_wino_kernel<KD, MB, MBW, TZ, TRW, GPC, Q4>;
+    auto kernel = conv_wino_kernel<KD, MB, MBW, TZ, TRW, GPC, Q4, ZSKIP>;
     if (int e = dmvs_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
     // persistent workgroups: as many as are resident at once (2 per CU by registers, fewer if the LDS stage is large)
     const unsigned resident = 256u * (unsigned)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));

@@ -361,6 +361,13 @@ extern long g_min_blocks, g_split_blocks, g_wino_stages, g_wino_persistent, g_wi
 extern long g_c8_rows;   // conv2d_c8.hip
 extern long g_k3r_grid, g_k3r_counted_wait;   // conv3d_coarse.hip
 extern long g_k3z_grid, g_k3z_zs;   // conv3d_zmarch.hip
+// 1: 3x3x3 launches on volumes of depth <= kZpadMaxDepth run the instantiations that skip zero-padding depth taps (common.h)
+long g_zpad_skip = 1;
+
+extern "C" long dmvs_zpad_live_mask(int form, int D, int oz0, int TZ) {
+    if (form < DMVS_ZFORM_S1 || form > DMVS_ZFORM_T2 || D < 1 || oz0 < 0 || TZ < 1 || TZ > 10) return -1;
+    return (long)zpad_live_mask(form, D, oz0, TZ);
+}
 
 extern "C" int dmvs_tune(const char* name, int value) {
     if (!name) return DMVS_EINVAL;
@@ -375,6 +382,7 @@ extern "C" int dmvs_tune(const char* name, int value) {
     if (!strcmp(name, "k3z_grid")) { if (value < 0 || value > 4096 || value % 8) return DMVS_EINVAL; g_k3z_grid = value; return 0; }
     if (!strcmp(name, "k3z_zs")) { if (value < 0 || value > 64) return DMVS_EINVAL; g_k3z_zs = value; return 0; }
     if (!strcmp(name, "k3r_counted_wait")) { g_k3r_counted_wait = value ? 1 : 0; return 0; }
+    if (!strcmp(name, "zpad_skip")) { if (value != 0 && value != 1) return DMVS_EINVAL; g_zpad_skip = value; return 0; }
     if (!strcmp(name, "wino_stages")) { if (value < 0 || value > 2) return DMVS_EINVAL; g_wino_stages = value; return 0; }
     return DMVS_EUNSUPPORTED;
 }

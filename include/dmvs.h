@@ -76,9 +76,16 @@ int dmvs_version(void);
  *   "c8_rows"                   rows per wave of the K3s row sweep (0 = chosen from the wave count)
  *   "k3z_grid"                  persistent workgroups of a K3z launch (dmvs_conv3d_zmarch; multiple of 8, 0 = as many as are resident)
  *   "k3z_zs"                    cap of a z segment's length in K3z (0 = none; results do not depend on it)
+ *   "zpad_skip"                 1 (default): 3x3x3 layers on volumes of depth <= 4 leave out the depth taps that only meet zero
+ *                               padding (dmvs_zpad_live_mask; value-equal for finite inputs); 0: every tap is multiplied (A/B + gate)
  * Returns 0, DMVS_EINVAL (bad value) or DMVS_EUNSUPPORTED (unknown name).  Process-wide, not thread-safe. */
 int dmvs_tune(const char* name, int value);
 const char* dmvs_error_string(int code);
+/* The live (plane, depth tap) pairs of a tile of TZ planes starting at plane oz0 of a 3x3x3 layer on a depth-D volume: bit
+ * 3 * p + kz is set when plane oz0 + p takes a plane that is not zero padding through tap kz.  form 0: stride 1 (output planes),
+ * 1: stride 2 (output planes of D -> (D + 1) / 2), 2: transposed stride 2 in gather form (input planes; tap 0 reads plane
+ * z + 1).  The kernels behind "zpad_skip" derive what they skip from this function.  -1: bad argument (TZ in 1..10). */
+long dmvs_zpad_live_mask(int form, int D, int oz0, int TZ);
 
 /* [C_total][H][W] planar slice c0..c0+C  ->  [H][W][C] pixel-major.
  * Layout glue between FeatureNet's NCHW output (module.py:326-336, the stageK / stageK_c channel
