@@ -88,6 +88,9 @@ SIGNATURES = {
     "dmvs_depth_regress": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "dmvs_depth_regress_backward": (_i, [_p, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "dmvs_dual_depth_loss_backward": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
+    "dmvs_conv3d_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "dmvs_conv3d_wgrad_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i]),
+    "dmvs_conv3d_wgrad_plan": (_i, [_i, _i, _i, _i, _i]),
 }
 
 EINVAL, EUNSUPPORTED = -1, -2   # include/dmvs.h

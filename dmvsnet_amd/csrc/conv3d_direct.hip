@@ -529,3 +529,6 @@ extern "C" int dmvs_conv3d_direct(const float* in, float* out, const float* w_pa
     }
     return DMVS_EINVAL;
 }
+
+// K3g: weight gradient of the stride-1 square layers (device code, launcher and its three C entries)
+#include "conv3d_wgrad.h"

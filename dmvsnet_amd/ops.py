@@ -868,3 +868,81 @@ def dual_depth_loss_backward(dsp_main: torch.Tensor, dsp_refine: torch.Tensor, g
                                                          _ptr(counts), _ptr(g_total), _ptr(g_main), _ptr(g_refine), _stream()),
                "dmvs_dual_depth_loss_backward")
     return g_main, g_refine
+
+
+# ------------------------------------------------------------------------------------------ K3g (training: the stride-1 square convs)
+WGRAD_TILE = (1, 4, 32)   # voxel tile (z, y, x) of K3g: dmvs_conv3d_wgrad_plan counts these (csrc/conv3d_wgrad.h)
+_pack_index_cache: dict = {}
+_wgrad_ws_cache: dict = {}
+
+
+def pack_index_mfma(C: int, kdepth: int, transposed_flipped: bool, device=None) -> torch.Tensor:
+    """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K3's weight packing for a stride-1 square layer
+    C -> C: for a weight ``w`` in nn.Conv3d / nn.Conv2d layout ``w.reshape(-1)[index] == pack_mfma(w, C, C, CONV_S1, kdepth)`` bit for
+    bit (the packing of these shapes is a pure permutation).  ``transposed_flipped``: the index of
+    ``pack_mfma(w.transpose(0, 1).flip(2, 3, 4), ...)`` instead -- the weight of the layer's data gradient.  Derived once on the host
+    by packing an iota through the library's packer."""
+    key = (int(C), int(kdepth), bool(transposed_flipped))
+    if device is not None and torch.device(device).type != "cpu":
+        dkey = key + (torch.device(device),)
+        idx = _pack_index_cache.get(dkey)
+        if idx is None:
+            idx = _pack_index_cache[dkey] = pack_index_mfma(C, kdepth, transposed_flipped).to(device)
+        return idx
+    idx = _pack_index_cache.get(key)
+    if idx is None:
+        n = C * C * 9 * kdepth
+        if kdepth not in (1, 3) or n >= (1 << 24):   # the iota travels as fp32
+            raise _lib.DmvsError(f"pack_index_mfma: C = {C}, kdepth = {kdepth}")
+        iota = torch.arange(n, dtype=torch.float32).reshape(C, C, kdepth, 3, 3)
+        if transposed_flipped:
+            iota = iota.transpose(0, 1).flip(2, 3, 4).contiguous()
+        packed = pack_mfma(iota, C, C, CONV_S1, kdepth)
+        if packed is None:
+            raise _lib.DmvsError(f"pack_index_mfma: K3 does not compile the stride-1 layer {C} -> {C}, kdepth {kdepth}")
+        idx = packed.to(torch.int64)
+        if idx.numel() != n or not torch.equal(torch.sort(idx).values, torch.arange(n)):
+            raise _lib.DmvsError(f"pack_index_mfma: the packing of {C} -> {C}, kdepth {kdepth} is not a permutation")
+        _pack_index_cache[key] = idx
+    return idx
+
+
+def conv3d_wgrad_workspace(C: int, D: int, H: int, W: int, kdepth: int, device) -> torch.Tensor:
+    """K3g's workspace, one per (shape class, device, stream): its size does not depend on the volume."""
+    n = _lib.load().dmvs_conv3d_wgrad_workspace(C, D, H, W, kdepth)
+    if n <= 0:
+        raise _lib.DmvsError(f"conv3d_wgrad: C = {C}, kdepth = {kdepth}, volume {(D, H, W)} is not covered by the weight-gradient kernel")
+    dev = torch.device(device)
+    key = (n, dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _wgrad_ws_cache.get(key)
+    if ws is None:
+        ws = _wgrad_ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
+    return ws
+
+
+def conv3d_wgrad(x: torch.Tensor, gy: torch.Tensor, kdepth: int, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K3g.  x, gy [C,D,H,W] (input of a stride-1 3x3(x3) pad-1 conv C -> C and the gradient on its output) -> the weight gradient
+    [C,C,kdepth,3,3].  ``out``: buffer to write into; with ``accumulate`` the result is ADDED to it (it must then be given).
+    ``workspace``: at least dmvs_conv3d_wgrad_workspace floats (default: a cached buffer per device and stream)."""
+    _req(x, gy, out, workspace)
+    if x.dim() != 4 or x.shape != gy.shape:
+        raise _lib.DmvsError(f"conv3d_wgrad: x {tuple(x.shape)} and gy {tuple(gy.shape)} must be the same [C,D,H,W]")
+    C, D, H, W = x.shape
+    if accumulate and out is None:
+        raise _lib.DmvsError("conv3d_wgrad: accumulate needs the buffer to add to (out)")
+    if out is None:
+        out = torch.empty((C, C, kdepth, 3, 3), dtype=torch.float32, device=x.device)
+    elif out.numel() != C * C * kdepth * 9:
+        raise _lib.DmvsError(f"conv3d_wgrad: out {tuple(out.shape)} is not a [{C},{C},{kdepth},3,3] weight")
+    if workspace is None:
+        workspace = conv3d_wgrad_workspace(C, D, H, W, kdepth, x.device)
+    elif workspace.numel() < _lib.load().dmvs_conv3d_wgrad_workspace(C, D, H, W, kdepth):
+        raise _lib.DmvsError("conv3d_wgrad: workspace too small")
+    cost = None
+    if timer is not None:
+        cost = (2.0 * 9 * kdepth * C * C * D * H * W, 4.0 * (2 * C * D * H * W + 9 * kdepth * C * C), None)
+    _launch(_lib.load().dmvs_conv3d_wgrad, (_ptr(x), _ptr(gy), _ptr(out), _ptr(workspace), C, D, H, W, kdepth, 1 if accumulate else 0),
+            f"wgrad{C}k{kdepth}", "wgrad", x, (gy, out, workspace), False, "conv3d_wgrad", cost)
+    _log("conv3d_wgrad")   # two dispatches per call: the partials and their sum (scripts/pmc_summary.py joins by dispatch order)
+    return out

@@ -514,6 +514,27 @@ int dmvs_dual_depth_loss_backward(const float* dsp_main, const float* dsp_refine
                                   int w, float weight, const long long* counts2, const float* g_total, float* g_dsp_main,
                                   float* g_dsp_refine, dmvs_stream_t stream);
 
+/* K3g: weight gradient of the stride-1 3x3(x3) pad-1 square convolutions on the fp32 matrix cores (csrc/conv3d_wgrad.h,
+ * docs/kernels/K3g_conv_wgrad.md) -- what autograd computes for the weight of the reference's Conv3d / Conv2d blocks
+ * (networks/module.py:28-70, 142) on conv2 / conv4 / conv6, the 2D conv6 and FeatureNet's conv1.1 / 1.2 / 2.1 / 2.2.
+ * (Their data gradient is dmvs_conv3d_mfma itself on the weight transposed in (co, ci) and flipped in every tap.)
+ *   x, gy      [C][D][H][W]: the layer's input and the gradient on its output
+ *   gw         [C][C][kdepth][3][3] out (nn.Conv3d / nn.Conv2d layout):
+ *              gw[co][ci][kz][ky][kx] (+)= sum_{z,y,x} gy[co][z][y][x] * x[ci][z+kz-1][y+ky-1][x+kx-1], zero outside the volume
+ *   workspace  dmvs_conv3d_wgrad_workspace(...) floats; partial sums, fully overwritten where read
+ *   accumulate 0: gw is overwritten; 1: the sum is added to gw (a batch runs as its samples one after the other)
+ * C in {16, 32, 64}, kdepth 3 or 1 (1: no z taps, D independent slices), else DMVS_EUNSUPPORTED; null pointers, empty sizes or more than
+ * 2^22 tiles: DMVS_EINVAL.  Two launches (partials, then their sum in a fixed order); no atomics: bitwise reproducible. */
+int dmvs_conv3d_wgrad(const float* x, const float* gy, float* gw, float* workspace, int C, int D, int H, int W, int kdepth,
+                      int accumulate, dmvs_stream_t stream);
+/* Workspace of dmvs_conv3d_wgrad in floats: one partial [9 * kdepth][C][C] per voxel share, 256 / (C / 32)^2 shares at most -- it does
+ * not depend on the volume.  0 for a shape the kernel is not compiled for. */
+long dmvs_conv3d_wgrad_workspace(int C, int D, int H, int W, int kdepth);
+/* Host only: the launch dmvs_conv3d_wgrad will make, as tiles * 512 + workgroups.  tiles = D * ceil(H / 4) * ceil(W / 32) voxel tiles
+ * of 1 x 4 x 32; workgroups = the size of the first launch's grid (a multiple of 8, at most 256); workgroups past
+ * min(tiles, 256 / blocks) * blocks, blocks = (C / 32)^2 or 1, exit at once and own no partial.  Negative DMVS_E* as dmvs_conv3d_wgrad. */
+int dmvs_conv3d_wgrad_plan(int C, int D, int H, int W, int kdepth);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,151 @@
+#!/usr/bin/env python
+"""Time and size forward + backward of the six stride-1 square convolutions on the product's kernels (dmvsnet_amd.DiffConv3d /
+DiffConv2d: K3 forward and data gradient, K3g weight gradient) against nn.Conv3d / nn.Conv2d on ATen (MIOpen) on the same MI355X, per
+sample (batch 1).
+
+Volumes per layer: the layer's volumes in the reference's training recipe (scripts/train.sh: 512 x 640, ndepths 48 / 32 / 8; rows
+"train.*") and in the config-2 stage passes (1184 x 1600, ndepths 64 / 32 / 8; rows "c2.*"): conv2 works at 1/2 of a stage's volume,
+conv4 at 1/4, conv6 at 1/8; the refine net has 4 hypotheses and a 2D bottleneck; FeatureNet's conv1.x / conv2.x work at 1/2 and 1/4 of
+the image.
+
+Both arms run in one process on one GPU, on the same tensors; every arm is warmed, and the timed windows alternate with the order
+swapped every round.  Per row and arm:
+  ms        device events around --reps repetitions, per repetition; median over the windows (min / max in the JSON)
+  peak_mb   torch.cuda.max_memory_allocated over one forward + backward, minus what was allocated before it
+and K3g alone: its time and its fraction of the 157 TFLOP/s fp32 MFMA peak at 2 * 9 * kd * C * C * D * H * W FLOP.
+One JSON line; --md writes the table of profiles/conv_train.md.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+from torch import nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT]
+
+PEAK_TF = 157.0
+
+# (row, C, kdepth, (D, H, W))
+ROWS = (
+    ("train.s1.conv2", 16, 3, (24, 64, 80)), ("train.s2.conv2", 16, 3, (16, 128, 160)), ("train.s3.conv2", 16, 3, (4, 256, 320)),
+    ("train.s1.conv4", 32, 3, (12, 32, 40)), ("train.s2.conv4", 32, 3, (8, 64, 80)), ("train.s3.conv4", 32, 3, (2, 128, 160)),
+    ("train.s1.conv6", 64, 3, (6, 16, 20)), ("train.s2.conv6", 64, 3, (4, 32, 40)), ("train.s3.conv6", 64, 3, (1, 64, 80)),
+    ("train.s3.refine.conv6", 64, 1, (1, 64, 80)),
+    ("train.feature.conv1.x", 16, 1, (1, 256, 320)), ("train.feature.conv2.x", 32, 1, (1, 128, 160)),
+    ("c2.s1.conv2", 16, 3, (32, 148, 200)), ("c2.s2.conv2", 16, 3, (16, 296, 400)), ("c2.s3.conv2", 16, 3, (4, 592, 800)),
+    ("c2.s1.conv4", 32, 3, (16, 74, 100)), ("c2.s2.conv4", 32, 3, (8, 148, 200)), ("c2.s3.conv4", 32, 3, (2, 296, 400)),
+    ("c2.s1.conv6", 64, 3, (8, 37, 50)), ("c2.s2.conv6", 64, 3, (4, 74, 100)), ("c2.s3.conv6", 64, 3, (1, 148, 200)),
+    ("c2.s3.refine.conv6", 64, 1, (1, 148, 200)),
+    ("c2.feature.conv1.x", 16, 1, (1, 592, 800)), ("c2.feature.conv2.x", 32, 1, (1, 296, 400)),
+)
+
+
+def spread(ts):
+    return dict(min=min(ts), median=float(np.median(ts)), max=max(ts), n=len(ts))
+
+
+def window(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def peak_mb(fn):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+
+def ab(arms, reps, windows):
+    """{"hip": fn, "aten": fn} -> row: every arm warmed, windows alternating with the order swapped every round."""
+    for fn in arms.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for w in range(windows):
+        for k in (("hip", "aten") if w % 2 == 0 else ("aten", "hip")):
+            ms[k].append(window(arms[k], reps))
+    r = {k + "_ms": spread(v) for k, v in ms.items()}
+    r.update({k + "_peak_mb": peak_mb(fn) for k, fn in arms.items()})
+    r["aten_over_hip"] = r["aten_ms"]["median"] / r["hip_ms"]["median"]
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--windows", type=int, default=4)
+    ap.add_argument("--rows", default="", help="comma-separated substrings: only the rows that contain one of them")
+    ap.add_argument("--md", default=None, help="also write the result table (markdown) to this file")
+    args = ap.parse_args()
+
+    from dmvsnet_amd import DiffConv2d, DiffConv3d, ops
+    assert torch.cuda.is_available(), "the benchmark needs the MI355X"
+    dev = torch.device("cuda:0")
+    out = dict(bench="conv_train", device=torch.cuda.get_device_name(0), reps=args.reps, windows=args.windows, rows={})
+    want = [s for s in args.rows.split(",") if s]
+    for name, C, kd, (D, H, W) in ROWS:
+        if want and not any(s in name for s in want):
+            continue
+        g = torch.Generator(device="cpu").manual_seed(C + kd + D)
+        shape = (1, C, D, H, W) if kd == 3 else (1, C, H, W)
+        x = torch.randn(shape, generator=g).to(dev).requires_grad_(True)
+        gy = torch.randn(shape, generator=g).to(dev)
+        hip = (DiffConv3d if kd == 3 else DiffConv2d)(C, C, 3, stride=1, padding=1, bias=False).to(dev)
+        aten = (nn.Conv3d if kd == 3 else nn.Conv2d)(C, C, 3, stride=1, padding=1, bias=False).to(dev)
+        aten.load_state_dict(hip.state_dict())
+
+        def arm(m):
+            return lambda: torch.autograd.grad(m(x), [x, m.weight], gy)
+
+        gh, ga = arm(hip)(), arm(aten)()
+        agree = max(((a - b).abs().max() / b.abs().max()).item() for a, b in zip(gh, ga))
+        r = ab({"hip": arm(hip), "aten": arm(aten)}, args.reps, args.windows)
+        x4, gy4 = x.detach().reshape(C, D, H, W), gy.reshape(C, D, H, W)
+        gw = torch.empty_like(hip.weight)
+        k3g = lambda: ops.conv3d_wgrad(x4, gy4, kd, out=gw)   # noqa: E731
+        k3g()
+        r["k3g_ms"] = float(np.median([window(k3g, args.reps) for _ in range(args.windows)]))
+        r["k3g_tflops"] = 2.0 * 9 * kd * C * C * D * H * W / (r["k3g_ms"] * 1e-3) / 1e12
+        r["k3g_peak_fraction"] = r["k3g_tflops"] / PEAK_TF
+        r.update(C=C, kd=kd, D=D, H=H, W=W, gradients_rel_diff=agree)
+        out["rows"][name] = r
+        print(f"# {name}: hip {r['hip_ms']['median']:.3f} ms  aten {r['aten_ms']['median']:.3f} ms  peak {r['hip_peak_mb']:.0f} / "
+              f"{r['aten_peak_mb']:.0f} MB  K3g {r['k3g_ms']:.3f} ms = {r['k3g_tflops']:.1f} TF  gradients differ by {agree:.1e}",
+              file=sys.stderr, flush=True)
+        del x, gy, gh, ga, hip, aten, gw
+    print(json.dumps(out))
+    if args.md:
+        with open(args.md, "w") as f:
+            f.write(markdown(out))
+
+
+def markdown(out):
+    lines = ["# Stride-1 square convolutions, forward + backward: K3 + K3g against nn.Conv3d / nn.Conv2d on ATen", "",
+             f"`scripts/conv_train_bench.py` on {out['device']}, one process, arms alternating; median of {out['windows']} windows of "
+             f"{out['reps']} repetitions, per sample (batch 1).  Times in ms, memory in MB (peak allocated over one forward + backward, "
+             "above what was allocated before).  K3g alone: its time and its fraction of the 157 TFLOP/s fp32 MFMA peak.", "",
+             "| layer | C | kd | D x H x W | hip fwd+bwd | ATen fwd+bwd | ATen / hip | hip peak | ATen peak | K3g | K3g TFLOP/s | of 157 | gradients, max rel. diff |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for name, r in out["rows"].items():
+        lines.append(f"| {name} | {r['C']} | {r['kd']} | {r['D']} x {r['H']} x {r['W']} | {r['hip_ms']['median']:.3f} | "
+                     f"{r['aten_ms']['median']:.3f} | {r['aten_over_hip']:.2f} | {r['hip_peak_mb']:.0f} | {r['aten_peak_mb']:.0f} | "
+                     f"{r['k3g_ms']:.3f} | {r['k3g_tflops']:.1f} | {r['k3g_peak_fraction']:.2f} | {r['gradients_rel_diff']:.1e} |")
+    lines.append("")
+    return "\n".join(lines)
+
+
+if __name__ == "__main__":
+    main()
