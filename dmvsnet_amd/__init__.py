@@ -12,8 +12,8 @@ from .costagg import DiffCostAgg, cost_agg  # noqa: F401  (differentiable cost a
 from . import head  # noqa: F401  (differentiable dual-depth head: K4 + K4b, and the dual-depth loss N6 + N6b)
 from .head import DiffDepthNet, diff_mvs_loss  # noqa: F401
 
-from . import conv  # noqa: F401  (differentiable stride-1 square convs: K3 forward / data gradient, K3g weight gradient)
-from .conv import DiffConv2d, DiffConv3d  # noqa: F401
+from . import conv  # noqa: F401  (differentiable convs: K3 forward / data gradient, K3g / K3h weight gradient)
+from .conv import DiffConv2d, DiffConv3d, DiffConvTranspose2d, DiffConvTranspose3d  # noqa: F401
 
 from . import eval_io  # noqa: F401  (PFM / cam I/O, eval dataset, Model.test step 1)
 from . import fusion   # noqa: F401  (geometric-consistency fusion filter, PLY)
@@ -25,4 +25,5 @@ from .validate import AbsDepthError_metrics, DTUValDataset, Thres_metrics, mvs_l
 __all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFeatures", "shard_source_views", "eval_io", "fusion",
            "cloud_eval", "reduce_points", "max_dist_cp", "point_compare", "scan_stats", "evaluate_dtu", "validate", "mvs_loss",
            "AbsDepthError_metrics", "Thres_metrics", "DTUValDataset", "run_validate", "DiffCostAgg", "cost_agg", "head", "DiffDepthNet",
-           "diff_mvs_loss", "conv", "DiffConv3d", "DiffConv2d"]
+           "diff_mvs_loss", "conv", "DiffConv3d", "DiffConv2d", "DiffConvTranspose3d",
+           "DiffConvTranspose2d"]

@@ -91,6 +91,9 @@ SIGNATURES = {
     "dmvs_conv3d_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dmvs_conv3d_wgrad_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i]),
     "dmvs_conv3d_wgrad_plan": (_i, [_i, _i, _i, _i, _i]),
+    "dmvs_conv3d_wgrad_s2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "dmvs_conv3d_wgrad_s2_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i]),
+    "dmvs_conv3d_wgrad_s2_plan": (_i, [_i, _i, _i, _i, _i]),
 }
 
 EINVAL, EUNSUPPORTED = -1, -2   # include/dmvs.h

@@ -1,5 +1,6 @@
-"""Differentiable stride-1 square convolutions of the regularisation U-Nets and FeatureNet: K3 forward and data gradient, K3g weight
-gradient, behind torch.autograd.
+"""Differentiable convolutions of the regularisation U-Nets and FeatureNet behind torch.autograd: the stride-1 square layers (K3 forward
+and data gradient, K3g weight gradient) and the stride-2 / transposed layers between them (K3 in both stride-2 modes, K3h weight
+gradient; second half of this text).
 
 ``DiffConv3d`` / ``DiffConv2d`` are ``nn.Conv3d`` / ``nn.Conv2d`` with another ``forward``: parameter name, shape, state-dict layout and
 ``isinstance(m, nn.Conv3d)`` initialisers are the reference's.  A reference user swaps the constructor inside the reference's blocks
@@ -7,10 +8,10 @@ gradient, behind torch.autograd.
 
     self.conv = dmvsnet_amd.DiffConv3d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
 
-Accepted: kernel 3, stride 1, padding 1, dilation 1, groups 1, no bias, in == out in {16, 32, 64} -- conv2 / conv4 / conv6 of
+Accepted at stride 1: kernel 3, padding 1, dilation 1, groups 1, no bias, in == out in {16, 32, 64} -- conv2 / conv4 / conv6 of
 CostRegNet_part, conv2 / conv4 and the 2D conv6 of CostRegNet_part_refine, conv1.1 / 1.2 / 2.1 / 2.2 and out2 of FeatureNet.  Everything
-else raises in the constructor: there is no ATen fallback.  BatchNorm, ReLU, the stride-2 and transposed layers, conv0 and ``prob``
-stay on ATen (``dmvsnet_amd.MVSNet.train()`` still raises).
+else raises in the constructor: there is no ATen fallback.  BatchNorm, ReLU, conv0, ``prob`` and FeatureNet's 5x5 stride-2 layers stay
+on ATen (``dmvsnet_amd.MVSNet.train()`` still raises).
 
 * forward: ``ops.conv3d(x[b], layer, backend="mfma")`` per sample, bit for bit, the layer being the bare convolution (no scale / shift /
   ReLU) with the weight packed on the device by one gather (``ops.pack_index_mfma``);
@@ -21,6 +22,18 @@ stay on ATen (``dmvsnet_amd.MVSNet.train()`` still raises).
 Autograd keeps the input and the weight only.  Both packed weights are cached per module, keyed on the weight's version counter, data
 pointer and device: an in-place optimiser step invalidates them, and after the first call a step makes no host copy and no host sync.
 fp32 on a HIP device only.  No atomics anywhere: forward and both gradients are bitwise reproducible.
+
+The stride-2 and transposed layers (kernel 3, stride 2, padding 1, no bias; transposed: output_padding 1, so fine extent = 2 x coarse):
+``DiffConv3d`` also takes stride 2 for (in, out) in {(8, 16), (16, 32), (32, 64)} (conv1 / 3 / 5), ``DiffConv2d`` for (32, 64) (the refine
+net's 2D conv5); ``DiffConvTranspose3d`` takes (64, 32), (32, 16), (16, 8) (conv7 / 9 / 11) and ``DiffConvTranspose2d`` (64, 32) (the 2D
+conv7).  The reference's ``Deconv3d`` / ``Deconv2d`` blocks swap ``nn.ConvTranspose3d`` / ``nn.ConvTranspose2d`` for them.
+
+* forward: K3's ``CONV_S2`` resp. ``DECONV_S2`` launch on the weight packed by one gather (``ops.pack_index_mfma_s2``);
+* data gradient: K3's launch in the OTHER mode, out -> in channels, on the SAME weight tensor -- no flip, no transposition: a
+  ConvTranspose weight is laid out [in][out], which is a conv weight's [out][in] read the other way.  For the stride-2 conv this
+  needs even input extents (H and W, and D for the 3D layers); odd ones are refused;
+* weight gradient: K3h (``ops.conv3d_wgrad_s2``) on (coarse, fine) = (dY, X) for the conv and (X, dY) for the transposed conv,
+  accumulated over the samples in batch order.
 """
 from __future__ import annotations
 
@@ -31,9 +44,11 @@ from torch.autograd.function import once_differentiable
 from . import ops
 from ._lib import DmvsError
 
-__all__ = ["DiffConv3d", "DiffConv2d", "launch_counts", "CHANNELS"]
+__all__ = ["DiffConv3d", "DiffConv2d", "DiffConvTranspose3d", "DiffConvTranspose2d", "launch_counts", "CHANNELS", "CHANNELS_S2"]
 
 CHANNELS = (16, 32, 64)   # the square shapes K3 and K3g compile
+# (fine, coarse) channels of the stride-2 / transposed layers K3 and K3h compile, per number of spatial dimensions
+CHANNELS_S2 = {3: ((8, 16), (16, 32), (32, 64)), 2: ((32, 64),)}
 
 # launches of the two backward paths since import (tests check through them that frozen inputs skip their kernel)
 launch_counts = {"dgrad": 0, "wgrad": 0}
@@ -86,8 +101,84 @@ class _ConvFn(torch.autograd.Function):
         return gx, gw, None, None
 
 
+def _packed_layer_s2(cache: dict, weight: torch.Tensor, kdepth: int, mode: int) -> ops.ConvLayer:
+    """The bare K3 layer that reads ``weight`` in ``mode``: CONV_S2 takes it as [out][in][k..], DECONV_S2 as [in][out][k..] -- the same
+    tensor either way, so a layer's forward and its data gradient are the two modes.  From the module's cache, keyed as _packed_layer."""
+    key = (weight._version, weight.data_ptr(), weight.device)
+    hit = cache.get(mode)
+    if hit is not None and hit[0] == key and hit[2] is weight:
+        return hit[1]
+    big, small = weight.shape[0], weight.shape[1]
+    cin, cout = (small, big) if mode == ops.CONV_S2 else (big, small)
+    index = ops.pack_index_mfma_s2(cin, cout, mode, kdepth, weight.device)
+    flat = weight.detach().reshape(-1)
+    packed = torch.index_select(torch.cat((flat, flat.new_zeros(1))), 0, index)   # a selection with zeros: the appended slot is the zero
+    layer = ops.ConvLayer("diff%s%dto%d" % ("conv_s2_" if mode == ops.CONV_S2 else "deconv_s2_", cin, cout), mode, kdepth, cin, cout, None,
+                          packed, None, None, False)
+    cache[mode] = (key, layer, weight)
+    return layer
+
+
+class _StridedFn(torch.autograd.Function):
+    """A stride-2 conv (``transposed`` False) or a transposed conv (True).  The weight is [coarse channels][fine channels][k..] in
+    both; the forward of the one is the data gradient of the other."""
+
+    @staticmethod
+    def forward(ctx, x, weight, kdepth, cache, transposed):
+        xd = x.detach()
+        fwd, bwd = (ops.DECONV_S2, ops.CONV_S2) if transposed else (ops.CONV_S2, ops.DECONV_S2)
+        layer = _packed_layer_s2(cache, weight, kdepth, fwd)
+        out = torch.empty((xd.shape[0], layer.cout, *layer.out_shape(*xd.shape[2:])), dtype=torch.float32, device=xd.device)
+        for b in range(xd.shape[0]):
+            ops.conv3d(xd[b], layer, out=out[b], backend="mfma")
+        ctx.save_for_backward(xd, weight)
+        ctx.kdepth, ctx.cache, ctx.transposed, ctx.bwd = kdepth, cache, transposed, bwd
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors   # (raises if the weight was changed in place since the forward)
+        gy = gy.contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            layer = _packed_layer_s2(ctx.cache, weight, ctx.kdepth, ctx.bwd)
+            gx = torch.empty_like(x)
+            for b in range(x.shape[0]):
+                ops.conv3d(gy[b], layer, out=gx[b], backend="mfma")
+                launch_counts["dgrad"] += 1
+        if ctx.needs_input_grad[1]:
+            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            for b in range(x.shape[0]):
+                coarse, fine = (x[b], gy[b]) if ctx.transposed else (gy[b], x[b])
+                ops.conv3d_wgrad_s2(coarse, fine, ctx.kdepth, out=gw, accumulate=b > 0)
+                launch_counts["wgrad"] += 1
+        return gx, gw, None, None, None
+
+
+def _check_even(what, x, nd):
+    if any(int(n) % 2 for n in x.shape[2:]):
+        raise DmvsError(f"{what}: the stride-2 layer needs even {'D, H, W' if nd == 3 else 'H, W'} (its data gradient is the transposed "
+                        f"layer with output_padding 1, and the U-Net's skip additions need them anyway); got {tuple(x.shape)}")
+
+
+def _check_ctor_transposed(what, nd, m):
+    one, two, three = (1,) * nd, (2,) * nd, (3,) * nd
+    pairs = tuple((co, ci) for ci, co in CHANNELS_S2[nd])
+    if m.kernel_size != three or m.stride != two or m.padding != one or m.output_padding != one or m.dilation != one or m.groups != 1 \
+            or m.bias is not None or m.padding_mode != "zeros" or (m.in_channels, m.out_channels) not in pairs:
+        raise DmvsError(f"{what}: only kernel 3, stride 2, padding 1, output_padding 1, dilation 1, groups 1, bias=False and (in, out) in "
+                        f"{pairs} run on the gfx950 kernels (no ATen fallback); got {m}")
+
+
 def _check_ctor(what, nd, m):
     one, three = (1,) * nd, (3,) * nd
+    if m.stride == (2,) * nd:
+        if m.kernel_size != three or m.padding != one or m.dilation != one or m.groups != 1 or m.bias is not None \
+                or m.padding_mode != "zeros" or (m.in_channels, m.out_channels) not in CHANNELS_S2[nd]:
+            raise DmvsError(f"{what}: at stride 2 only kernel 3, padding 1, dilation 1, groups 1, bias=False and (in, out) in "
+                            f"{CHANNELS_S2[nd]} run on the gfx950 kernels (no ATen fallback); got {m}")
+        return
     if m.kernel_size != three or m.stride != one or m.padding != one or m.dilation != one or m.groups != 1 or m.bias is not None \
             or m.padding_mode != "zeros" or m.in_channels != m.out_channels or m.in_channels not in CHANNELS:
         raise DmvsError(f"{what}: only kernel 3, stride 1, padding 1, dilation 1, groups 1, bias=False and in == out in {CHANNELS} run "
@@ -114,7 +205,8 @@ def _check_weight(what, w, x):
 
 class DiffConv3d(nn.Conv3d):
     """``nn.Conv3d(C, C, 3, stride=1, padding=1, bias=False)``, C in {16, 32, 64}, on K3 (forward, data gradient) and K3g (weight
-    gradient).  Input [B,C,D,H,W], fp32, contiguous, on a HIP device."""
+    gradient); or ``nn.Conv3d(C, 2 * C, 3, stride=2, padding=1, bias=False)``, C in {8, 16, 32}, on K3 and K3h (even D, H, W).  Input
+    [B,C,D,H,W], fp32, contiguous, on a HIP device."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -124,13 +216,18 @@ class DiffConv3d(nn.Conv3d):
     def forward(self, x):
         _check_input("DiffConv3d", x, 3, self.in_channels)
         _check_weight("DiffConv3d", self.weight, x)
+        if self.stride[0] == 2:
+            _check_even("DiffConv3d", x, 3)
         with torch.cuda.device(x.device):
+            if self.stride[0] == 2:
+                return _StridedFn.apply(x, self.weight, 3, self._packed, False)
             return _ConvFn.apply(x, self.weight, 3, self._packed)
 
 
 class DiffConv2d(nn.Conv2d):
-    """``nn.Conv2d(C, C, 3, stride=1, padding=1, bias=False)``, C in {16, 32, 64}, on the kdepth-1 forms of K3 and K3g.  Input
-    [B,C,H,W], fp32, contiguous, on a HIP device; each sample is a D = 1 volume."""
+    """``nn.Conv2d(C, C, 3, stride=1, padding=1, bias=False)``, C in {16, 32, 64}, on the kdepth-1 forms of K3 and K3g; or
+    ``nn.Conv2d(32, 64, 3, stride=2, padding=1, bias=False)`` on those of K3 and K3h (even H, W).  Input [B,C,H,W], fp32, contiguous, on
+    a HIP device; each sample is a D = 1 volume."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -140,5 +237,46 @@ class DiffConv2d(nn.Conv2d):
     def forward(self, x):
         _check_input("DiffConv2d", x, 2, self.in_channels)
         _check_weight("DiffConv2d", self.weight, x)
+        if self.stride[0] == 2:
+            _check_even("DiffConv2d", x, 2)
         with torch.cuda.device(x.device):
+            if self.stride[0] == 2:
+                return _StridedFn.apply(x.unsqueeze(2), self.weight, 1, self._packed, False).squeeze(2)
             return _ConvFn.apply(x.unsqueeze(2), self.weight, 1, self._packed).squeeze(2)
+
+
+class DiffConvTranspose3d(nn.ConvTranspose3d):
+    """``nn.ConvTranspose3d(2 * C, C, 3, stride=2, padding=1, output_padding=1, bias=False)``, C in {32, 16, 8}, on K3 (forward: the
+    transposed launch; data gradient: the stride-2 launch on the same weight) and K3h (weight gradient).  Input [B,2C,D,H,W], fp32,
+    contiguous, on a HIP device; output [B,C,2D,2H,2W]."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        _check_ctor_transposed("DiffConvTranspose3d", 3, self)
+        self._packed = {}
+
+    def forward(self, x, output_size=None):
+        if output_size is not None:
+            raise DmvsError("DiffConvTranspose3d: output_size is not supported (the output is twice the input)")
+        _check_input("DiffConvTranspose3d", x, 3, self.in_channels)
+        _check_weight("DiffConvTranspose3d", self.weight, x)
+        with torch.cuda.device(x.device):
+            return _StridedFn.apply(x, self.weight, 3, self._packed, True)
+
+
+class DiffConvTranspose2d(nn.ConvTranspose2d):
+    """``nn.ConvTranspose2d(64, 32, 3, stride=2, padding=1, output_padding=1, bias=False)`` on the kdepth-1 forms of K3 and K3h.  Input
+    [B,64,H,W], fp32, contiguous, on a HIP device; output [B,32,2H,2W]."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        _check_ctor_transposed("DiffConvTranspose2d", 2, self)
+        self._packed = {}
+
+    def forward(self, x, output_size=None):
+        if output_size is not None:
+            raise DmvsError("DiffConvTranspose2d: output_size is not supported (the output is twice the input)")
+        _check_input("DiffConvTranspose2d", x, 2, self.in_channels)
+        _check_weight("DiffConvTranspose2d", self.weight, x)
+        with torch.cuda.device(x.device):
+            return _StridedFn.apply(x.unsqueeze(2), self.weight, 1, self._packed, True).squeeze(2)

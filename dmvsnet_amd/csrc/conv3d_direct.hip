@@ -532,3 +532,6 @@ extern "C" int dmvs_conv3d_direct(const float* in, float* out, const float* w_pa
 
 // K3g: weight gradient of the stride-1 square layers (device code, launcher and its three C entries)
 #include "conv3d_wgrad.h"
+
+// K3h: weight gradient of the stride-2 and the transposed layers (device code, launcher and its three C entries)
+#include "conv3d_wgrad_s2.h"

@@ -946,3 +946,98 @@ def conv3d_wgrad(x: torch.Tensor, gy: torch.Tensor, kdepth: int, out: Optional[t
             f"wgrad{C}k{kdepth}", "wgrad", x, (gy, out, workspace), False, "conv3d_wgrad", cost)
     _log("conv3d_wgrad")   # two dispatches per call: the partials and their sum (scripts/pmc_summary.py joins by dispatch order)
     return out
+
+
+# ------------------------------------------------------------------------------------------ K3h (training: the stride-2 and transposed convs)
+# coarse voxel tile (z, y, x) of K3h per (Ca, kdepth): dmvs_conv3d_wgrad_s2_plan counts these (csrc/conv3d_wgrad_s2.h)
+WGRAD_S2_TILE = {(16, 3): (1, 4, 32), (32, 3): (1, 4, 32), (64, 3): (1, 2, 32), (64, 1): (1, 4, 32)}
+_wgrad_s2_ws_cache: dict = {}
+
+
+def pack_index_mfma_s2(cin: int, cout: int, mode: int, kdepth: int, device=None) -> torch.Tensor:
+    """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K3's weight packing for a stride-2 layer
+    (``mode`` CONV_S2, weight [cout][cin][k..]) or a transposed one (DECONV_S2, weight [cin][cout][k..]) with cout = 2 cin resp.
+    cin = 2 cout: ``torch.cat((w.reshape(-1), zeros(1)))[index] == pack_mfma(w, cin, cout, mode, kdepth)`` bit for bit.  These
+    packings are selections with zeros, not permutations (conv1's packed-K form pads its last k-step, conv11's y-parity-merged form has
+    zero rows): a zero of the packed form selects the one appended zero slot, index n = cin * cout * 9 * kdepth.  Derived once on the
+    host by packing ``iota + 1`` through the library's packer; every weight element must be selected exactly once."""
+    key = ("s2", int(cin), int(cout), int(mode), int(kdepth))
+    if device is not None and torch.device(device).type != "cpu":
+        dkey = key + (torch.device(device),)
+        idx = _pack_index_cache.get(dkey)
+        if idx is None:
+            idx = _pack_index_cache[dkey] = pack_index_mfma_s2(cin, cout, mode, kdepth).to(device)
+        return idx
+    idx = _pack_index_cache.get(key)
+    if idx is None:
+        n = cin * cout * 9 * kdepth
+        ok = (mode == CONV_S2 and cout == 2 * cin) or (mode == DECONV_S2 and cin == 2 * cout)
+        if not ok or kdepth not in (1, 3) or n < 1 or n + 1 >= (1 << 24):   # the iota travels as fp32
+            raise _lib.DmvsError(f"pack_index_mfma_s2: {cin} -> {cout}, mode {mode}, kdepth {kdepth} is no stride-2 or transposed layer")
+        lead = (cout, cin) if mode == CONV_S2 else (cin, cout)
+        iota = (torch.arange(n, dtype=torch.float32) + 1.0).reshape(*lead, kdepth, 3, 3)
+        packed = pack_mfma(iota, cin, cout, mode, kdepth)
+        if packed is None:
+            raise _lib.DmvsError(f"pack_index_mfma_s2: K3 does not compile the layer {cin} -> {cout}, mode {mode}, kdepth {kdepth}")
+        idx = packed.to(torch.int64) - 1
+        idx[idx < 0] = n
+        if not torch.equal(torch.bincount(idx, minlength=n + 1)[:n], torch.ones(n, dtype=torch.int64)):
+            raise _lib.DmvsError(f"pack_index_mfma_s2: the packing of {cin} -> {cout}, mode {mode}, kdepth {kdepth} does not select every "
+                                 "weight element exactly once")
+        _pack_index_cache[key] = idx
+    return idx
+
+
+def _wgrad_s2_dims(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int):
+    if coarse.dim() != 4 or fine.dim() != 4:
+        raise _lib.DmvsError(f"conv3d_wgrad_s2: coarse {tuple(coarse.shape)} and fine {tuple(fine.shape)} must be [C,D,H,W]")
+    Ca, Dc, Hc, Wc = coarse.shape
+    want = (Ca // 2, 2 * Dc if kdepth == 3 else Dc, 2 * Hc, 2 * Wc)
+    if Ca % 2 or tuple(fine.shape) != want:
+        raise _lib.DmvsError(f"conv3d_wgrad_s2: the fine tensor of coarse {tuple(coarse.shape)}, kdepth {kdepth} is {want}, got "
+                             f"{tuple(fine.shape)}")
+    return Ca, Dc, Hc, Wc
+
+
+def conv3d_wgrad_s2_workspace(Ca: int, Dc: int, Hc: int, Wc: int, kdepth: int, device) -> torch.Tensor:
+    """K3h's workspace, one per (shape class, device, stream): its size does not depend on the volume."""
+    n = _lib.load().dmvs_conv3d_wgrad_s2_workspace(Ca, Dc, Hc, Wc, kdepth)
+    if n <= 0:
+        raise _lib.DmvsError(f"conv3d_wgrad_s2: Ca = {Ca}, kdepth = {kdepth}, coarse volume {(Dc, Hc, Wc)} is not covered by the strided "
+                             "weight-gradient kernel")
+    dev = torch.device(device)
+    key = (n, dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _wgrad_s2_ws_cache.get(key)
+    if ws is None:
+        ws = _wgrad_s2_ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
+    return ws
+
+
+def conv3d_wgrad_s2(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K3h.  coarse [Ca,Dc,Hc,Wc], fine [Ca/2,Df,2Hc,2Wc] (Df = 2 Dc, or Dc for kdepth 1) -> G [Ca,Ca/2,kdepth,3,3],
+    G[a,b,kz,ky,kx] = sum coarse[a,z,y,x] * fine[b,2z+kz-1,2y+ky-1,2x+kx-1].  Stride-2 conv (kernel 3, padding 1): coarse = the gradient
+    on the output, fine = the input, G = dW.  Transposed conv (output_padding 1): coarse = the input, fine = the gradient on the output,
+    G = dWt.  ``out``: buffer to write into; with ``accumulate`` the result is ADDED to it (it must then be given).
+    ``workspace``: at least dmvs_conv3d_wgrad_s2_workspace floats (default: a cached buffer per device and stream)."""
+    _req(coarse, fine, out, workspace)
+    Ca, Dc, Hc, Wc = _wgrad_s2_dims(coarse, fine, kdepth)
+    if accumulate and out is None:
+        raise _lib.DmvsError("conv3d_wgrad_s2: accumulate needs the buffer to add to (out)")
+    if out is None:
+        out = torch.empty((Ca, Ca // 2, kdepth, 3, 3), dtype=torch.float32, device=coarse.device)
+    elif out.numel() != Ca * (Ca // 2) * kdepth * 9:
+        raise _lib.DmvsError(f"conv3d_wgrad_s2: out {tuple(out.shape)} is not a [{Ca},{Ca // 2},{kdepth},3,3] weight")
+    if workspace is None:
+        workspace = conv3d_wgrad_s2_workspace(Ca, Dc, Hc, Wc, kdepth, coarse.device)
+    elif workspace.numel() < _lib.load().dmvs_conv3d_wgrad_s2_workspace(Ca, Dc, Hc, Wc, kdepth):
+        raise _lib.DmvsError("conv3d_wgrad_s2: workspace too small")
+    cost = None
+    if timer is not None:
+        nt = 9 * kdepth * Ca * (Ca // 2)
+        cost = (2.0 * nt * Dc * Hc * Wc, 4.0 * (coarse.numel() + fine.numel() + nt), None)
+    _launch(_lib.load().dmvs_conv3d_wgrad_s2,
+            (_ptr(coarse), _ptr(fine), _ptr(out), _ptr(workspace), Ca, Dc, Hc, Wc, kdepth, 1 if accumulate else 0),
+            f"wgrad_s2_{Ca}k{kdepth}", "wgrad_s2", coarse, (fine, out, workspace), False, "conv3d_wgrad_s2", cost)
+    _log("conv3d_wgrad_s2")   # two dispatches per call: the partials and their sum
+    return out

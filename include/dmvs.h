@@ -535,6 +535,31 @@ long dmvs_conv3d_wgrad_workspace(int C, int D, int H, int W, int kdepth);
  * min(tiles, 256 / blocks) * blocks, blocks = (C / 32)^2 or 1, exit at once and own no partial.  Negative DMVS_E* as dmvs_conv3d_wgrad. */
 int dmvs_conv3d_wgrad_plan(int C, int D, int H, int W, int kdepth);
 
+/* K3h: weight gradient of the stride-2 and the transposed 3x3(x3) convolutions (kernel 3, stride 2, padding 1; transposed:
+ * output_padding 1) on the fp32 matrix cores (csrc/conv3d_wgrad_s2.h, docs/kernels/K3h_conv_wgrad_s2.md) -- what autograd computes
+ * for the weight of conv1 / 3 / 5 and conv7 / 9 / 11 of the regularisation U-Nets and the 2D conv5 / conv7 of the refine net.
+ * (Their data gradient is dmvs_conv3d_mfma in the OTHER stride-2 mode on the same weight tensor.)
+ *   coarse     [Ca][Dc][Hc][Wc]: the gradient on a stride-2 conv's output, or the input of a transposed conv
+ *   fine       [Ca / 2][Df][2 Hc][2 Wc], Df = 2 Dc (kdepth 3) or Dc (kdepth 1): the conv's input, or the gradient on the transposed
+ *              conv's output
+ *   gw         [Ca][Ca / 2][kdepth][3][3] out -- nn.Conv3d's [out][in] and nn.ConvTranspose3d's [in][out] alike:
+ *              gw[a][b][kz][ky][kx] (+)= sum_{z,y,x} coarse[a][z][y][x] * fine[b][2z+kz-1][2y+ky-1][2x+kx-1], zero outside `fine`
+ *              (kdepth 1: plane z, no kz)
+ *   workspace  dmvs_conv3d_wgrad_s2_workspace(...) floats; partial sums, fully overwritten where read
+ *   accumulate 0: gw is overwritten; 1: the sum is added to gw (a batch runs as its samples one after the other)
+ * (Ca, kdepth) in {(16, 3), (32, 3), (64, 3), (64, 1)}, else DMVS_EUNSUPPORTED; null pointers, empty sizes, an extent above 2^20 or more
+ * than 2^22 tiles: DMVS_EINVAL.  Two launches (partials, then their sum in a fixed order); no atomics: bitwise reproducible. */
+int dmvs_conv3d_wgrad_s2(const float* coarse, const float* fine, float* gw, float* workspace, int Ca, int Dc, int Hc, int Wc, int kdepth,
+                         int accumulate, dmvs_stream_t stream);
+/* Workspace of dmvs_conv3d_wgrad_s2 in floats: one partial [9 * kdepth][Ca][Ca / 2] per voxel share, 256 (Ca = 64: 128) shares at most
+ * -- it does not depend on the volume.  0 for a shape the kernel is not compiled for. */
+long dmvs_conv3d_wgrad_s2_workspace(int Ca, int Dc, int Hc, int Wc, int kdepth);
+/* Host only: the launch dmvs_conv3d_wgrad_s2 will make, as tiles * 512 + workgroups.  tiles = Dc * ceil(Hc / TY) * ceil(Wc / 32) coarse
+ * voxel tiles of 1 x TY x 32, TY = 4 (2 for Ca = 64, kdepth 3); workgroups = the size of the first launch's grid (a multiple of 8, at
+ * most 256); workgroups past min(tiles, 256 / blocks) * blocks, blocks = 2 for Ca = 64, else 1, exit at once and own no partial.
+ * Negative DMVS_E* as dmvs_conv3d_wgrad_s2. */
+int dmvs_conv3d_wgrad_s2_plan(int Ca, int Dc, int Hc, int Wc, int kdepth);
+
 #ifdef __cplusplus
 }
 #endif

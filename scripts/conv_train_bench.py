@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Time and size forward + backward of the six stride-1 square convolutions on the product's kernels (dmvsnet_amd.DiffConv3d /
 DiffConv2d: K3 forward and data gradient, K3g weight gradient) against nn.Conv3d / nn.Conv2d on ATen (MIOpen) on the same MI355X, per
-sample (batch 1).
+sample (batch 1); and of the eight stride-2 / transposed layers between them (DiffConv3d / DiffConv2d at stride 2,
+DiffConvTranspose3d / DiffConvTranspose2d: K3 in both stride-2 modes, K3h weight gradient) against nn.Conv3d / nn.ConvTranspose3d and
+the 2D forms.  A strided row is named after its layer (conv1 / 3 / 5 going down, conv7 / 9 / 11 going up, the refine net's 2D conv5 /
+conv7); its coarse volume is the volume of the square layer it sits next to (conv1 and conv11: conv2's, ...), its fine one twice that.
 
 Volumes per layer: the layer's volumes in the reference's training recipe (scripts/train.sh: 512 x 640, ndepths 48 / 32 / 8; rows
 "train.*") and in the config-2 stage passes (1184 x 1600, ndepths 64 / 32 / 8; rows "c2.*"): conv2 works at 1/2 of a stage's volume,
@@ -12,7 +15,8 @@ Both arms run in one process on one GPU, on the same tensors; every arm is warme
 swapped every round.  Per row and arm:
   ms        device events around --reps repetitions, per repetition; median over the windows (min / max in the JSON)
   peak_mb   torch.cuda.max_memory_allocated over one forward + backward, minus what was allocated before it
-and K3g alone: its time and its fraction of the 157 TFLOP/s fp32 MFMA peak at 2 * 9 * kd * C * C * D * H * W FLOP.
+and the weight-gradient kernel alone (K3g, or K3h on the strided rows): its time and its fraction of the 157 TFLOP/s fp32 MFMA peak at
+2 * 9 * kd * Cout * Cin * (output voxels of the GEMM's reduction: D * H * W, coarse for K3h) FLOP.
 One JSON line; --md writes the table of profiles/conv_train.md.
 """
 import argparse
@@ -42,6 +46,25 @@ ROWS = (
     ("c2.s3.refine.conv6", 64, 1, (1, 148, 200)),
     ("c2.feature.conv1.x", 16, 1, (1, 592, 800)), ("c2.feature.conv2.x", 32, 1, (1, 296, 400)),
 )
+
+
+# the strided neighbours of a square row: (suffix of the square layer, stride-2 conv going down, transposed conv going up)
+NEIGHBOURS = (("refine.conv6", "refine.conv5", "refine.conv7"), (".conv2", ".conv1", ".conv11"), (".conv4", ".conv3", ".conv9"),
+              (".conv6", ".conv5", ".conv7"))
+
+
+def strided_rows():
+    """(row, mode, Ca, kdepth, coarse (D, H, W)) of the eight layers at every volume of ROWS they occur at."""
+    rows = []
+    for name, C, kd, vol in ROWS:
+        if "feature" in name:
+            continue
+        for suffix, down, up in NEIGHBOURS:
+            if name.endswith(suffix):
+                stem = name[:-len(suffix)]
+                rows += [(stem + down, "conv", C, kd, vol), (stem + up, "deconv", C, kd, vol)]
+                break
+    return rows
 
 
 def spread(ts):
@@ -126,6 +149,45 @@ def main():
               f"{r['aten_peak_mb']:.0f} MB  K3g {r['k3g_ms']:.3f} ms = {r['k3g_tflops']:.1f} TF  gradients differ by {agree:.1e}",
               file=sys.stderr, flush=True)
         del x, gy, gh, ga, hip, aten, gw
+    from dmvsnet_amd import DiffConvTranspose2d, DiffConvTranspose3d
+    for name, mode, Ca, kd, (D, H, W) in strided_rows():
+        if want and not any(s in name for s in want):
+            continue
+        Cb = Ca // 2
+        g = torch.Generator(device="cpu").manual_seed(Ca + kd + D + 1)
+        cshape = (1, Ca, D, H, W) if kd == 3 else (1, Ca, H, W)
+        fshape = (1, Cb, 2 * D, 2 * H, 2 * W) if kd == 3 else (1, Cb, 2 * H, 2 * W)
+        xshape, yshape = (fshape, cshape) if mode == "conv" else (cshape, fshape)
+        x = torch.randn(xshape, generator=g).to(dev).requires_grad_(True)
+        gy = torch.randn(yshape, generator=g).to(dev)
+        if mode == "conv":
+            hip = (DiffConv3d if kd == 3 else DiffConv2d)(Cb, Ca, 3, stride=2, padding=1, bias=False).to(dev)
+            aten = (nn.Conv3d if kd == 3 else nn.Conv2d)(Cb, Ca, 3, stride=2, padding=1, bias=False).to(dev)
+        else:
+            hip = (DiffConvTranspose3d if kd == 3 else DiffConvTranspose2d)(Ca, Cb, 3, stride=2, padding=1, output_padding=1, bias=False).to(dev)
+            aten = (nn.ConvTranspose3d if kd == 3 else nn.ConvTranspose2d)(Ca, Cb, 3, stride=2, padding=1, output_padding=1, bias=False).to(dev)
+        aten.load_state_dict(hip.state_dict())
+
+        def arm(m):
+            return lambda: torch.autograd.grad(m(x), [x, m.weight], gy)
+
+        gh, ga = arm(hip)(), arm(aten)()
+        agree = max(((a - b).abs().max() / b.abs().max()).item() for a, b in zip(gh, ga))
+        r = ab({"hip": arm(hip), "aten": arm(aten)}, args.reps, args.windows)
+        coarse, fine = (gy, x.detach()) if mode == "conv" else (x.detach(), gy)
+        c4, f4 = coarse.reshape(Ca, D, H, W), fine.reshape(Cb, 2 * D if kd == 3 else D, 2 * H, 2 * W)
+        gw = torch.empty_like(hip.weight)
+        k3h = lambda: ops.conv3d_wgrad_s2(c4, f4, kd, out=gw)   # noqa: E731
+        k3h()
+        r["k3g_ms"] = float(np.median([window(k3h, args.reps) for _ in range(args.windows)]))
+        r["k3g_tflops"] = 2.0 * 9 * kd * Ca * Cb * D * H * W / (r["k3g_ms"] * 1e-3) / 1e12
+        r["k3g_peak_fraction"] = r["k3g_tflops"] / PEAK_TF
+        r.update(C=f"{Cb}->{Ca}" if mode == "conv" else f"{Ca}->{Cb}", kd=kd, D=D, H=H, W=W, gradients_rel_diff=agree, kernel="K3h")
+        out["rows"][name] = r
+        print(f"# {name}: hip {r['hip_ms']['median']:.3f} ms  aten {r['aten_ms']['median']:.3f} ms  peak {r['hip_peak_mb']:.0f} / "
+              f"{r['aten_peak_mb']:.0f} MB  K3h {r['k3g_ms']:.3f} ms = {r['k3g_tflops']:.1f} TF  gradients differ by {agree:.1e}",
+              file=sys.stderr, flush=True)
+        del x, gy, gh, ga, hip, aten, gw
     print(json.dumps(out))
     if args.md:
         with open(args.md, "w") as f:
@@ -133,11 +195,12 @@ def main():
 
 
 def markdown(out):
-    lines = ["# Stride-1 square convolutions, forward + backward: K3 + K3g against nn.Conv3d / nn.Conv2d on ATen", "",
+    lines = ["# Regularisation and feature convolutions, forward + backward: K3 + K3g / K3h against ATen", "",
              f"`scripts/conv_train_bench.py` on {out['device']}, one process, arms alternating; median of {out['windows']} windows of "
              f"{out['reps']} repetitions, per sample (batch 1).  Times in ms, memory in MB (peak allocated over one forward + backward, "
-             "above what was allocated before).  K3g alone: its time and its fraction of the 157 TFLOP/s fp32 MFMA peak.", "",
-             "| layer | C | kd | D x H x W | hip fwd+bwd | ATen fwd+bwd | ATen / hip | hip peak | ATen peak | K3g | K3g TFLOP/s | of 157 | gradients, max rel. diff |",
+             "above what was allocated before).  wgrad: the weight-gradient kernel alone (K3g; K3h on the stride-2 / transposed rows, "
+             "whose C is in -> out and whose D x H x W is the coarse volume), its time and its fraction of the 157 TFLOP/s fp32 MFMA peak.", "",
+             "| layer | C | kd | D x H x W | hip fwd+bwd | ATen fwd+bwd | ATen / hip | hip peak | ATen peak | wgrad | wgrad TFLOP/s | of 157 | gradients, max rel. diff |",
              "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
     for name, r in out["rows"].items():
         lines.append(f"| {name} | {r['C']} | {r['kd']} | {r['D']} x {r['H']} x {r['W']} | {r['hip_ms']['median']:.3f} | "

@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Generate tests/golden/op_conv_s2_grad.npz by RUNNING THE REFERENCE's stride-2 and transposed blocks under fp32 autograd on the CPU.
+
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_conv_s2_grad.py <path of the reference checkout>
+
+Imports networks/module.py of the reference (read-only, never copied).  For every case of tests/conv_s2_grad_ref.GOLDEN_CASES it
+builds the reference's block -- ``Conv3d(C, 2C, stride=2, padding=1)``, ``Deconv3d(2C, C, stride=2, padding=1, output_padding=1)``,
+``Conv2d(32, 64, 3, stride=2, padding=1)`` or ``Deconv2d(64, 32, 3, stride=2, padding=1, output_padding=1)``: layer + TRAIN-mode
+BatchNorm + ReLU --, loads the case's weight and BatchNorm gamma / beta, runs it on the input and back-propagates the upstream gradient.
+Stored per case, data only: x, w, gamma, beta, gy, the block's output and the gradients for x, w, gamma and beta -- activations as
+[B,C,D,H,W] (2D: D = 1), weights as [Ca,Cb,kd,3,3] (the layer's own layout with a kd axis).
+
+Asserted on every case before it is stored (the tests re-assert it on the stored data): no BatchNorm output within 1e-5 of the ReLU
+kink (tests/conv_s2_grad_ref.kink_violations).  Printed per case: ``e_ref``, the distance of the reference's fp32 results to the float64
+restatement, normalised by the tensor's max-abs.  64 <-> 32 in 3D is left to the float64 tests: its weight gradient alone is 221 KB.
+The file is asserted to stay under the repository's limit for a committed file (1 MiB).
+"""
+import contextlib
+import io
+import os
+import sys
+import warnings
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if len(sys.argv) != 2 or not os.path.isfile(os.path.join(sys.argv[1], "networks", "module.py")):
+    sys.exit(__doc__)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, sys.argv[1])
+warnings.filterwarnings("ignore")
+
+import conv_s2_grad_ref as R  # noqa: E402
+
+with contextlib.redirect_stdout(io.StringIO()):
+    from networks import module as ref_module  # noqa: E402
+
+torch.set_num_threads(8)
+
+
+def run_reference(case):
+    Cb, kd, mode = case["Cb"], case["kd"], case["mode"]
+    x, w = case["x"].clone(), case["w"]
+    if kd == 3:
+        block = ref_module.Conv3d(Cb, 2 * Cb, stride=2, padding=1) if mode == "conv" else \
+            ref_module.Deconv3d(2 * Cb, Cb, stride=2, padding=1, output_padding=1)
+    else:
+        block = ref_module.Conv2d(Cb, 2 * Cb, 3, stride=2, padding=1) if mode == "conv" else \
+            ref_module.Deconv2d(2 * Cb, Cb, 3, stride=2, padding=1, output_padding=1)
+        x, w = x.squeeze(2), w.squeeze(2)
+    assert block.conv.bias is None and block.bn is not None and block.relu
+    assert tuple(block.conv.weight.shape) == tuple(w.shape)
+    with torch.no_grad():
+        block.conv.weight.copy_(w)
+        block.bn.weight.copy_(case["gamma"])
+        block.bn.bias.copy_(case["beta"])
+    block.train()
+    x.requires_grad_(True)
+    out = block(x)
+    gy = case["gy"] if kd == 3 else case["gy"].squeeze(2)
+    assert out.shape == gy.shape, (out.shape, gy.shape)
+    out.backward(gy)
+    u = (lambda t: t) if kd == 3 else (lambda t: t.unsqueeze(2))
+    return dict(out=u(out.detach()), g_x=u(x.grad), g_w=u(block.conv.weight.grad), g_gamma=block.bn.weight.grad, g_beta=block.bn.bias.grad)
+
+
+def main():
+    arrs = {}
+    for name, kw in R.GOLDEN_CASES.items():
+        case = R.make_case(**kw)
+        assert R.kink_violations(case) == 0, (name, "a BatchNorm output sits on the ReLU kink: pick another seed")
+        ref = run_reference(case)
+        f64 = R.block_f64(case)
+        e = {k: R.rel_dist(ref[k], f64[k]) for k in ("out", "g_x", "g_w", "g_gamma", "g_beta")}
+        print(f"{name}: e_ref " + "  ".join(f"{k} {v:.2e}" for k, v in e.items()))
+        assert max(e.values()) < 1e-5, (name, e)   # sanity only: the same function, not a test bound
+        for k in ("x", "w", "gamma", "beta", "gy"):
+            arrs[f"{name}.{k}"] = case[k].numpy()
+        for k, v in ref.items():
+            arrs[f"{name}.{k}"] = v.contiguous().numpy()
+    path = os.path.join(HERE, "op_conv_s2_grad.npz")
+    np.savez_compressed(path, **arrs)
+    size = os.path.getsize(path)
+    print(f"op_conv_s2_grad.npz: {size / 1024:.1f} KB, keys={len(arrs)}")
+    assert size < (1 << 20)
+
+
+if __name__ == "__main__":
+    main()
