@@ -15,6 +15,10 @@ from .head import DiffDepthNet, diff_mvs_loss  # noqa: F401
 from . import conv  # noqa: F401  (differentiable convs: K3 forward / data gradient, K3g / K3h weight gradient)
 from .conv import DiffConv2d, DiffConv3d, DiffConvTranspose2d, DiffConvTranspose3d  # noqa: F401
 
+from . import bn  # noqa: F401  (differentiable BatchNorm + ReLU: K5 forward / backward, and the four U-Net blocks on it)
+from .bn import (DiffBatchNormReLU2d, DiffBatchNormReLU3d, DiffConvBlock2d, DiffConvBlock3d, DiffDeconvBlock2d,  # noqa: F401
+                 DiffDeconvBlock3d)
+
 from . import eval_io  # noqa: F401  (PFM / cam I/O, eval dataset, Model.test step 1)
 from . import fusion   # noqa: F401  (geometric-consistency fusion filter, PLY)
 from . import cloud_eval  # noqa: F401  (DTU accuracy / completeness of a fused cloud)
@@ -26,4 +30,5 @@ __all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFea
            "cloud_eval", "reduce_points", "max_dist_cp", "point_compare", "scan_stats", "evaluate_dtu", "validate", "mvs_loss",
            "AbsDepthError_metrics", "Thres_metrics", "DTUValDataset", "run_validate", "DiffCostAgg", "cost_agg", "head", "DiffDepthNet",
            "diff_mvs_loss", "conv", "DiffConv3d", "DiffConv2d", "DiffConvTranspose3d",
-           "DiffConvTranspose2d"]
+           "DiffConvTranspose2d", "bn", "DiffBatchNormReLU3d", "DiffBatchNormReLU2d", "DiffConvBlock3d", "DiffDeconvBlock3d",
+           "DiffConvBlock2d", "DiffDeconvBlock2d"]

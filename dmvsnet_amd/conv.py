@@ -10,8 +10,9 @@ gradient; second half of this text).
 
 Accepted at stride 1: kernel 3, padding 1, dilation 1, groups 1, no bias, in == out in {16, 32, 64} -- conv2 / conv4 / conv6 of
 CostRegNet_part, conv2 / conv4 and the 2D conv6 of CostRegNet_part_refine, conv1.1 / 1.2 / 2.1 / 2.2 and out2 of FeatureNet.  Everything
-else raises in the constructor: there is no ATen fallback.  BatchNorm, ReLU, conv0, ``prob`` and FeatureNet's 5x5 stride-2 layers stay
-on ATen (``dmvsnet_amd.MVSNet.train()`` still raises).
+else raises in the constructor: there is no ATen fallback.  conv0, ``prob`` and FeatureNet's 5x5 stride-2 layers stay on ATen
+(``dmvsnet_amd.MVSNet.train()`` still raises); BatchNorm + ReLU run on K5 (``dmvsnet_amd.bn``: ``DiffBatchNormReLU3d`` / ``2d``, and the
+blocks ``DiffConvBlock3d`` ... that pair these layers with it).
 
 * forward: ``ops.conv3d(x[b], layer, backend="mfma")`` per sample, bit for bit, the layer being the bare convolution (no scale / shift /
   ReLU) with the weight packed on the device by one gather (``ops.pack_index_mfma``);

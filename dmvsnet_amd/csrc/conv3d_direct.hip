@@ -535,3 +535,6 @@ extern "C" int dmvs_conv3d_direct(const float* in, float* out, const float* w_pa
 
 // K3h: weight gradient of the stride-2 and the transposed layers (device code, launcher and its three C entries)
 #include "conv3d_wgrad_s2.h"
+
+// K5: train- and eval-mode BatchNorm + ReLU, forward and backward (device code, launchers and its five C entries)
+#include "batchnorm.h"

@@ -1041,3 +1041,115 @@ def conv3d_wgrad_s2(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int, out: 
             f"wgrad_s2_{Ca}k{kdepth}", "wgrad_s2", coarse, (fine, out, workspace), False, "conv3d_wgrad_s2", cost)
     _log("conv3d_wgrad_s2")   # two dispatches per call: the partials and their sum
     return out
+
+
+# ------------------------------------------------------------------------------------------ K5 (training: BatchNorm + ReLU)
+BN_CHANNELS = (8, 16, 32, 64)   # the channel counts K5 takes (csrc/batchnorm.h)
+BN_CHUNK = 1024                 # elements of a chunk: 256 lanes x 4 floats; a share is a run of whole chunks
+BN_MAX_WG = 2048                # workgroups of a launch at most: Smax = BN_MAX_WG // C shares per channel
+BN_TRAIN = 32                   # include/dmvs.h DMVS_BN_TRAIN
+_bn_ws_cache: dict = {}
+
+
+def _bn_dims(x: torch.Tensor):
+    if x.dim() < 3:
+        raise _lib.DmvsError(f"bn_relu: the input must be [B,C,...], got {tuple(x.shape)}")
+    B, C = int(x.shape[0]), int(x.shape[1])
+    V = 1
+    for n in x.shape[2:]:
+        V *= int(n)
+    return B, C, V
+
+
+def bn_plan(C: int, B: int, V: int) -> int:
+    """Shares S a channel of B * V elements is cut into by every K5 launch (grid: C * S workgroups)."""
+    S = _lib.load().dmvs_bn_plan(C, B, V)
+    if S <= 0:
+        raise _lib.DmvsError(f"bn_relu: C = {C}, B = {B}, V = {V} is not covered by the BatchNorm kernels (C in {BN_CHANNELS})")
+    return S
+
+
+def bn_share_range(C: int, B: int, V: int, s: int):
+    """[lo, hi) of the flattened (b, v) index that share s owns: the partition function the kernels call."""
+    lo, hi = ctypes.c_long(), ctypes.c_long()
+    _lib.check(_lib.load().dmvs_bn_share_range(C, B, V, s, ctypes.byref(lo), ctypes.byref(hi)), "bn_share_range")
+    return lo.value, hi.value
+
+
+def bn_workspace(C: int, B: int, V: int, device) -> torch.Tensor:
+    """K5's workspace, one per (size, device, stream): its size does not depend on the volume."""
+    n = _lib.load().dmvs_bn_workspace(C, B, V)
+    if n <= 0:
+        raise _lib.DmvsError(f"bn_relu: C = {C}, B = {B}, V = {V} is not covered by the BatchNorm kernels (C in {BN_CHANNELS})")
+    dev = torch.device(device)
+    if dev.index is None:   # "cuda" and "cuda:<current>" are one device and must be one workspace
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    key = (n, dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _bn_ws_cache.get(key)
+    if ws is None:
+        ws = _bn_ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
+    return ws
+
+
+def _bn_vectors(what: str, C: int, x: torch.Tensor, *vs: torch.Tensor) -> None:
+    for v in vs:
+        if v.numel() != C or v.device != x.device:
+            raise _lib.DmvsError(f"{what}: a per-channel vector has {v.numel()} elements on {v.device}, the input {C} channels on {x.device}")
+
+
+def bn_relu_forward(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor, running_var: torch.Tensor,
+                    momentum: float, eps: float, relu: bool, training: bool, workspace: Optional[torch.Tensor] = None):
+    """K5 forward.  x [B,C,...] -> (y, mean, invstd): y = relu(BatchNorm(x)) (``relu`` False: no ReLU), mean / invstd [C] as the
+    backward takes them.  ``training``: batch statistics, and running_mean / running_var are blended in place (momentum, unbiased
+    variance); else the running statistics are used and left alone."""
+    _req(x, gamma, beta, running_mean, running_var, workspace)
+    B, C, V = _bn_dims(x)
+    _bn_vectors("bn_relu_forward", C, x, gamma, beta, running_mean, running_var)
+    if training and B * V < 2:
+        raise _lib.DmvsError(f"bn_relu_forward: train mode needs more than one value per channel, got input {tuple(x.shape)}")
+    if workspace is None:
+        workspace = bn_workspace(C, B, V, x.device)
+    elif workspace.numel() < _lib.load().dmvs_bn_workspace(C, B, V):
+        raise _lib.DmvsError("bn_relu_forward: workspace too small")
+    y = torch.empty_like(x)
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    flags = (RELU if relu else 0) | (BN_TRAIN if training else 0)
+    cost = None
+    if timer is not None:
+        cost = (5.0 * B * C * V, 4.0 * B * C * V * (3 if training else 2), None)
+    _launch(_lib.load().dmvs_bn_relu_forward,
+            (_ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(y), _ptr(mean), _ptr(invstd), _ptr(workspace),
+             B, C, V, float(momentum), float(eps), flags),
+            f"bn{C}", "bn_relu_forward", x, (gamma, beta, running_mean, running_var, workspace), False, "batchnorm", cost)
+    if training:
+        _log("batchnorm")   # two dispatches in train mode: the partial statistics, then fold + apply
+    return y, mean, invstd
+
+
+def bn_relu_backward(x: torch.Tensor, gy: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                     relu: bool, training: bool, need_gx: bool = True, workspace: Optional[torch.Tensor] = None):
+    """K5 backward.  x (the forward's input), gy, and the forward's gamma / beta / mean / invstd -> (gx | None, g_gamma, g_beta).  The
+    ReLU mask is recomputed from x; the forward's output is not needed.  ``need_gx`` False skips the apply launch."""
+    _req(x, gy, gamma, beta, mean, invstd, workspace)
+    if gy.shape != x.shape:
+        raise _lib.DmvsError(f"bn_relu_backward: x {tuple(x.shape)} and gy {tuple(gy.shape)} must have the same shape")
+    B, C, V = _bn_dims(x)
+    _bn_vectors("bn_relu_backward", C, x, gamma, beta, mean, invstd)
+    if workspace is None:
+        workspace = bn_workspace(C, B, V, x.device)
+    elif workspace.numel() < _lib.load().dmvs_bn_workspace(C, B, V):
+        raise _lib.DmvsError("bn_relu_backward: workspace too small")
+    gx = torch.empty_like(x) if need_gx else None
+    g_gamma = torch.empty(C, dtype=torch.float32, device=x.device)
+    g_beta = torch.empty(C, dtype=torch.float32, device=x.device)
+    flags = (RELU if relu else 0) | (BN_TRAIN if training else 0)
+    cost = None
+    if timer is not None:
+        cost = (12.0 * B * C * V, 4.0 * B * C * V * (5 if need_gx else 2), None)
+    _launch(_lib.load().dmvs_bn_relu_backward,
+            (_ptr(x), _ptr(gy), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(gx), _ptr(g_gamma), _ptr(g_beta), _ptr(workspace),
+             B, C, V, flags),
+            f"bn{C}", "bn_relu_backward", x, (gy, gamma, beta, mean, invstd, workspace), False, "batchnorm", cost)
+    _log("batchnorm")   # two dispatches: the partial sums, then fold + apply (or the fold alone)
+    return gx, g_gamma, g_beta

@@ -45,6 +45,7 @@ typedef void* dmvs_stream_t; /* hipStream_t */
                               view's half is one contiguous [C/4][H][W][4] map): FeatureNet's stageK / stageK_c halves
                               (module.py:326-336) written directly in the layout dmvs_warp_corr_q4 samples; K3 conv
                               modes, no residual, Cout % 8 == 0 */
+#define DMVS_BN_TRAIN 32   /* dmvs_bn_relu_forward / _backward only: batch statistics (train mode); without it the running ones (eval) */
 #define DMVS_IN_VIEWS 16   /* dmvs_conv3d_mfma, Cin = 4, kdepth 1, DMVS_CONV_S1 only (FeatureNet's first layer, module.py:283): `in`
                               is the eval loader's image stack [D = V][3][H][W] (general_eval.py:89,186) read in place -- channel c
                               of view v at ((v * 3 + c) * H * W) -- instead of a planar [4][V][H][W] copy with a zero channel.  The
@@ -559,6 +560,40 @@ long dmvs_conv3d_wgrad_s2_workspace(int Ca, int Dc, int Hc, int Wc, int kdepth);
  * most 256); workgroups past min(tiles, 256 / blocks) * blocks, blocks = 2 for Ca = 64, else 1, exit at once and own no partial.
  * Negative DMVS_E* as dmvs_conv3d_wgrad_s2. */
 int dmvs_conv3d_wgrad_s2_plan(int Ca, int Dc, int Hc, int Wc, int kdepth);
+
+/* K5: BatchNorm + ReLU of the reference's Conv3d / Deconv3d / Conv2d / Deconv2d blocks (networks/module.py: `self.bn(...)`, then
+ * `F.relu(x, inplace=True)`), forward and backward, train and eval mode (csrc/batchnorm.h, docs/kernels/K5_batchnorm_relu.md).
+ *   x, y, gy, gx   [B][C][V] fp32, V = D * H * W (2D layers: H * W); the batch is handled inside the kernels
+ *   gamma, beta, mean, invstd, running_mean, running_var, g_gamma, g_beta   [C]
+ *   flags          DMVS_RELU: y = max(pre, 0) and the gradient is masked by [pre > 0]; DMVS_BN_TRAIN: batch statistics
+ *   workspace      dmvs_bn_workspace(...) floats: per-share partial sums, fully overwritten where read
+ * Forward, train: pre = fmaf(x - mean, invstd * gamma, beta) with mean and the BIASED variance of the B * V elements of a channel
+ * (invstd = 1 / sqrt(var + eps)); mean / invstd are stored for the backward; running_mean = (1 - momentum) * running_mean + momentum *
+ * mean, running_var likewise with the UNBIASED variance var * n / (n - 1).  Two launches (partial statistics; fold + apply).
+ * Forward, eval: mean = running_mean, invstd = 1 / sqrt(running_var + eps) (both also stored to mean / invstd); the running buffers are
+ * only read.  One launch.
+ * Backward: g = gy * [pre > 0] with pre RECOMPUTED from x by the forward's own function (y is not an argument);
+ * g_beta = sum g, g_gamma = sum g * xhat, xhat = (x - mean) * invstd; gx = gamma * invstd * (g - g_beta / n - xhat * g_gamma / n) in train
+ * mode, gamma * invstd * g in eval mode.  gx may be NULL: g_gamma / g_beta alone.  Two launches.
+ * The variance is formed from sums around a per-channel pivot (never E[x^2] - E[x]^2 of the raw values); partials are added in a fixed
+ * order in fp64.  No atomics: bitwise reproducible.
+ * DMVS_EINVAL: C not in {8, 16, 32, 64}, a null pointer (other than gx), B < 1, V < 1, B * V < 2 in train mode, B * V above 2^31 - 2^13,
+ * unknown flag bits, momentum outside [0, 1], eps < 0. */
+int dmvs_bn_relu_forward(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
+                         float* mean, float* invstd, float* workspace, int B, int C, int V, float momentum, float eps, int flags,
+                         dmvs_stream_t stream);
+int dmvs_bn_relu_backward(const float* x, const float* gy, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                          float* gx, float* g_gamma, float* g_beta, float* workspace, int B, int C, int V, int flags,
+                          dmvs_stream_t stream);
+/* Workspace of the two in floats: [C][Smax][2] partials and [C] pivots, Smax = 2048 / C -- it does not depend on the volume.  0 for
+ * arguments the kernels refuse. */
+long dmvs_bn_workspace(int C, int B, int V);
+/* Host only: the number of shares S = min(ceil(B * V / 1024), 2048 / C) every K5 launch cuts a channel into (grid: C * S workgroups of
+ * 256 lanes; a chunk is 256 lanes x 4 floats).  DMVS_EINVAL as above. */
+int dmvs_bn_plan(int C, int B, int V);
+/* Host only: the range [*lo, *hi) of the flattened index b * V + v that share s of a channel owns -- the very function the kernels call.
+ * Whole chunks [s * chunks / S, (s + 1) * chunks / S), the last one cut at B * V.  DMVS_EINVAL as above, and for s outside [0, S). */
+int dmvs_bn_share_range(int C, int B, int V, int s, long* lo, long* hi);
 
 #ifdef __cplusplus
 }
