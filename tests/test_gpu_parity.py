@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 from dmvsnet_amd import MVSNet, ops, synth  # noqa: E402
 from dmvsnet_amd._lib import DmvsError  # noqa: E402
 from oracle import dmvs_oracle as O  # noqa: E402
+from warp_corr_ref import _q4_window_pieces  # noqa: E402
 
 DEV = "cuda:0"
 T = torch.from_numpy
@@ -1143,23 +1144,6 @@ def test_warp_corr_behind_camera_and_far_outside(C, k1):
     # the behind-camera taps mirror through the image centre with a huge magnification: compare where the oracle is smooth
     diff = (sim.cpu() - want[0]).abs()
     assert diff.mean() < 2e-5 and (diff > 1e-3).float().mean() < 1e-3
-
-
-def _q4_window_pieces(sx, ox, sy, oy, H, W):
-    """Window sizes (16-byte pieces per quad plane) the q4 kernel stages for every 32 x 8 tile under the projection
-    ix = sx * x + ox, iy = sy * y + oy (depth-independent): the corner bound of warp_corr.hip restated on the host."""
-    out = set()
-    f = np.float32
-    for ty in range(0, H, 8):
-        for tx in range(0, W, 32):
-            xs = [f(sx) * f(x) + f(ox) for x in (tx, min(tx + 31, W - 1))]
-            ys = [f(sy) * f(y) + f(oy) for y in (ty, min(ty + 7, H - 1))]
-            cx = np.clip(xs, -1.0, W)
-            cy = np.clip(ys, -1.0, H)
-            x0, x1 = max(int(np.floor(cx.min() - 1 / 64)), -1), min(int(np.floor(cx.max() + 1 / 64)) + 1, W + 1)
-            y0, y1 = max(int(np.floor(cy.min() - 1 / 64)), -1), min(int(np.floor(cy.max() + 1 / 64)) + 1, H + 1)
-            out.add((x1 - x0 + 1) * (y1 - y0 + 1))
-    return out
 
 
 @pytest.mark.parametrize("C,variant,targets", [(32, 0, (318, 319, 637, 638)), (16, 0, (637, 638)),
