@@ -19,6 +19,9 @@ from . import bn  # noqa: F401  (differentiable BatchNorm + ReLU: K5 forward / b
 from .bn import (DiffBatchNormReLU2d, DiffBatchNormReLU3d, DiffConvBlock2d, DiffConvBlock3d, DiffDeconvBlock2d,  # noqa: F401
                  DiffDeconvBlock3d)
 
+from . import regnet  # noqa: F401  (the four regularisation networks on the differentiable layers; conv0 / prob: K2 + K2g)
+from .regnet import DiffCostRegNet, DiffCostRegNetPart, DiffCostRegNetPartRefine, DiffCostRegNetRefine  # noqa: F401
+
 from . import eval_io  # noqa: F401  (PFM / cam I/O, eval dataset, Model.test step 1)
 from . import fusion   # noqa: F401  (geometric-consistency fusion filter, PLY)
 from . import cloud_eval  # noqa: F401  (DTU accuracy / completeness of a fused cloud)
@@ -31,4 +34,5 @@ __all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFea
            "AbsDepthError_metrics", "Thres_metrics", "DTUValDataset", "run_validate", "DiffCostAgg", "cost_agg", "head", "DiffDepthNet",
            "diff_mvs_loss", "conv", "DiffConv3d", "DiffConv2d", "DiffConvTranspose3d",
            "DiffConvTranspose2d", "bn", "DiffBatchNormReLU3d", "DiffBatchNormReLU2d", "DiffConvBlock3d", "DiffDeconvBlock3d",
-           "DiffConvBlock2d", "DiffDeconvBlock2d"]
+           "DiffConvBlock2d", "DiffDeconvBlock2d", "regnet", "DiffCostRegNetPart", "DiffCostRegNetPartRefine", "DiffCostRegNet",
+           "DiffCostRegNetRefine"]

@@ -94,6 +94,9 @@ SIGNATURES = {
     "dmvs_conv3d_wgrad_s2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dmvs_conv3d_wgrad_s2_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i]),
     "dmvs_conv3d_wgrad_s2_plan": (_i, [_i, _i, _i, _i, _i]),
+    "dmvs_conv3d_wgrad_c2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "dmvs_conv3d_wgrad_c2_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i]),
+    "dmvs_conv3d_wgrad_c2_plan": (_i, [_i, _i, _i, _i, _i]),
     "dmvs_bn_relu_forward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _i, _p]),
     "dmvs_bn_relu_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "dmvs_bn_workspace": (ctypes.c_long, [_i, _i, _i]),

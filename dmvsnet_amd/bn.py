@@ -25,8 +25,9 @@ raises in the constructor: there is no ATen fallback.  fp32, contiguous, on a HI
 
 ``DiffConvBlock3d`` / ``DiffDeconvBlock3d`` / ``DiffConvBlock2d`` / ``DiffDeconvBlock2d`` take the reference blocks' constructor
 arguments and have their children (``.conv``, ``.bn``) and state-dict keys; each is a ``DiffConv*`` / ``DiffConvTranspose*`` layer and a
-``DiffBatchNormReLU*``.  ``bn=False`` or a layer shape the convolution classes refuse raises (the 2-channel ends ``conv0`` / ``prob`` keep
-the reference's block, ``conv0`` with only its ``.bn`` swapped).
+``DiffBatchNormReLU*``.  ``bn=False`` or a layer shape the convolution classes refuse raises.  ``DiffConvBlock3d(2, 8, 3, padding=1)`` is
+conv0 as the reference builds it; ``prob`` has no BatchNorm and is a bare ``DiffConv3d(8, 2, ...)`` (``dmvsnet_amd.regnet`` builds the
+whole networks).
 """
 from __future__ import annotations
 

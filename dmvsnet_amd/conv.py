@@ -1,6 +1,7 @@
 """Differentiable convolutions of the regularisation U-Nets and FeatureNet behind torch.autograd: the stride-1 square layers (K3 forward
-and data gradient, K3g weight gradient) and the stride-2 / transposed layers between them (K3 in both stride-2 modes, K3h weight
-gradient; second half of this text).
+and data gradient, K3g weight gradient), the stride-2 / transposed layers between them (K3 in both stride-2 modes, K3h weight
+gradient; second part of this text) and the U-Nets' 2-channel ends conv0 / ``prob`` (K2 forward and data gradient, K2g weight gradient;
+third part).
 
 ``DiffConv3d`` / ``DiffConv2d`` are ``nn.Conv3d`` / ``nn.Conv2d`` with another ``forward``: parameter name, shape, state-dict layout and
 ``isinstance(m, nn.Conv3d)`` initialisers are the reference's.  A reference user swaps the constructor inside the reference's blocks
@@ -10,9 +11,9 @@ gradient; second half of this text).
 
 Accepted at stride 1: kernel 3, padding 1, dilation 1, groups 1, no bias, in == out in {16, 32, 64} -- conv2 / conv4 / conv6 of
 CostRegNet_part, conv2 / conv4 and the 2D conv6 of CostRegNet_part_refine, conv1.1 / 1.2 / 2.1 / 2.2 and out2 of FeatureNet.  Everything
-else raises in the constructor: there is no ATen fallback.  conv0, ``prob`` and FeatureNet's 5x5 stride-2 layers stay on ATen
+else raises in the constructor: there is no ATen fallback.  FeatureNet's 5x5 stride-2 and 1x1 layers stay on ATen
 (``dmvsnet_amd.MVSNet.train()`` still raises); BatchNorm + ReLU run on K5 (``dmvsnet_amd.bn``: ``DiffBatchNormReLU3d`` / ``2d``, and the
-blocks ``DiffConvBlock3d`` ... that pair these layers with it).
+blocks ``DiffConvBlock3d`` ... that pair these layers with it); ``dmvsnet_amd.regnet`` builds the four regularisation networks.
 
 * forward: ``ops.conv3d(x[b], layer, backend="mfma")`` per sample, bit for bit, the layer being the bare convolution (no scale / shift /
   ReLU) with the weight packed on the device by one gather (``ops.pack_index_mfma``);
@@ -35,6 +36,14 @@ conv7).  The reference's ``Deconv3d`` / ``Deconv2d`` blocks swap ``nn.ConvTransp
   needs even input extents (H and W, and D for the 3D layers); odd ones are refused;
 * weight gradient: K3h (``ops.conv3d_wgrad_s2``) on (coarse, fine) = (dY, X) for the conv and (X, dY) for the transposed conv,
   accumulated over the samples in batch order.
+
+The 2-channel ends (kernel 3, stride 1, padding 1, no bias): ``DiffConv3d`` also takes (in, out) = (2, 8) -- conv0 -- and (8, 2) --
+``prob``.  ``DiffConv2d`` does not: no 2D layer has these shapes.  Each one's data gradient has the other one's shape:
+
+* forward: ``ops.conv3d(x[b], layer, backend="direct")`` per sample, bit for bit: K2's ``cout2`` kernel for 8 -> 2 and its
+  ``Cin == 2`` direct form for 2 -> 8, the weight packed on the device by one gather (``ops.pack_index_direct``);
+* data gradient: the OTHER of those two launches on the weight transposed in (co, ci) and flipped in every tap;
+* weight gradient: K2g (``ops.conv3d_wgrad_c2``), accumulated over the samples in batch order.
 """
 from __future__ import annotations
 
@@ -45,11 +54,13 @@ from torch.autograd.function import once_differentiable
 from . import ops
 from ._lib import DmvsError
 
-__all__ = ["DiffConv3d", "DiffConv2d", "DiffConvTranspose3d", "DiffConvTranspose2d", "launch_counts", "CHANNELS", "CHANNELS_S2"]
+__all__ = ["DiffConv3d", "DiffConv2d", "DiffConvTranspose3d", "DiffConvTranspose2d", "launch_counts", "CHANNELS", "CHANNELS_S2",
+           "CHANNELS_C2"]
 
 CHANNELS = (16, 32, 64)   # the square shapes K3 and K3g compile
 # (fine, coarse) channels of the stride-2 / transposed layers K3 and K3h compile, per number of spatial dimensions
 CHANNELS_S2 = {3: ((8, 16), (16, 32), (32, 64)), 2: ((32, 64),)}
+CHANNELS_C2 = ops.WGRAD_C2_SHAPES   # (in, out) of the 2-channel ends K2 and K2g run: conv0 and prob (3D only)
 
 # launches of the two backward paths since import (tests check through them that frozen inputs skip their kernel)
 launch_counts = {"dgrad": 0, "wgrad": 0}
@@ -157,6 +168,57 @@ class _StridedFn(torch.autograd.Function):
         return gx, gw, None, None, None
 
 
+def _packed_layer_c2(cache: dict, weight: torch.Tensor, transposed_flipped: bool) -> ops.ConvLayer:
+    """The bare K2 layer of ``weight`` ([8,2,3,3,3] or [2,8,3,3,3]) or of its transposed-flipped form (a layer out -> in), from the
+    module's cache, keyed as _packed_layer."""
+    key = (weight._version, weight.data_ptr(), weight.device)
+    hit = cache.get(transposed_flipped)
+    if hit is not None and hit[0] == key and hit[2] is weight:
+        return hit[1]
+    cout, cin = weight.shape[0], weight.shape[1]
+    index = ops.pack_index_direct(cin, cout, transposed_flipped, weight.device)
+    packed = torch.index_select(weight.detach().reshape(-1), 0, index)   # one device gather: the packing is a permutation
+    lin, lout = (cout, cin) if transposed_flipped else (cin, cout)
+    layer = ops.ConvLayer("diffconv%dto%d%s" % (cin, cout, "t" if transposed_flipped else ""), ops.CONV_S1, 3, lin, lout, packed, None,
+                          None, None, False)
+    cache[transposed_flipped] = (key, layer, weight)
+    return layer
+
+
+class _EndFn(torch.autograd.Function):
+    """conv0 (2 -> 8) or prob (8 -> 2) on K2: the forward of the one has the shape of the data gradient of the other."""
+
+    @staticmethod
+    def forward(ctx, x, weight, cache):
+        xd = x.detach()
+        layer = _packed_layer_c2(cache, weight, False)
+        out = torch.empty((xd.shape[0], layer.cout, *xd.shape[2:]), dtype=torch.float32, device=xd.device)
+        for b in range(xd.shape[0]):
+            ops.conv3d(xd[b], layer, out=out[b], backend="direct")
+        ctx.save_for_backward(xd, weight)
+        ctx.cache = cache
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors   # (raises if the weight was changed in place since the forward)
+        gy = gy.contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            layer = _packed_layer_c2(ctx.cache, weight, True)
+            gx = torch.empty_like(x)
+            for b in range(x.shape[0]):
+                ops.conv3d(gy[b], layer, out=gx[b], backend="direct")
+                launch_counts["dgrad"] += 1
+        if ctx.needs_input_grad[1]:
+            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            for b in range(x.shape[0]):
+                ops.conv3d_wgrad_c2(x[b], gy[b], out=gw, accumulate=b > 0)
+                launch_counts["wgrad"] += 1
+        return gx, gw, None
+
+
 def _check_even(what, x, nd):
     if any(int(n) % 2 for n in x.shape[2:]):
         raise DmvsError(f"{what}: the stride-2 layer needs even {'D, H, W' if nd == 3 else 'H, W'} (its data gradient is the transposed "
@@ -180,10 +242,12 @@ def _check_ctor(what, nd, m):
             raise DmvsError(f"{what}: at stride 2 only kernel 3, padding 1, dilation 1, groups 1, bias=False and (in, out) in "
                             f"{CHANNELS_S2[nd]} run on the gfx950 kernels (no ATen fallback); got {m}")
         return
+    square = m.in_channels == m.out_channels and m.in_channels in CHANNELS
+    ends = nd == 3 and (m.in_channels, m.out_channels) in CHANNELS_C2
     if m.kernel_size != three or m.stride != one or m.padding != one or m.dilation != one or m.groups != 1 or m.bias is not None \
-            or m.padding_mode != "zeros" or m.in_channels != m.out_channels or m.in_channels not in CHANNELS:
-        raise DmvsError(f"{what}: only kernel 3, stride 1, padding 1, dilation 1, groups 1, bias=False and in == out in {CHANNELS} run "
-                        f"on the gfx950 kernels (no ATen fallback); got {m}")
+            or m.padding_mode != "zeros" or not (square or ends):
+        raise DmvsError(f"{what}: only kernel 3, stride 1, padding 1, dilation 1, groups 1, bias=False and in == out in {CHANNELS}"
+                        f"{f' or (in, out) in {CHANNELS_C2}' if nd == 3 else ''} run on the gfx950 kernels (no ATen fallback); got {m}")
 
 
 def _check_input(what, x, nd, C):
@@ -206,7 +270,8 @@ def _check_weight(what, w, x):
 
 class DiffConv3d(nn.Conv3d):
     """``nn.Conv3d(C, C, 3, stride=1, padding=1, bias=False)``, C in {16, 32, 64}, on K3 (forward, data gradient) and K3g (weight
-    gradient); or ``nn.Conv3d(C, 2 * C, 3, stride=2, padding=1, bias=False)``, C in {8, 16, 32}, on K3 and K3h (even D, H, W).  Input
+    gradient); or ``nn.Conv3d(C, 2 * C, 3, stride=2, padding=1, bias=False)``, C in {8, 16, 32}, on K3 and K3h (even D, H, W); or
+    ``nn.Conv3d(2, 8, 3, stride=1, padding=1, bias=False)`` / ``nn.Conv3d(8, 2, ...)``, conv0 / ``prob``, on K2 and K2g.  Input
     [B,C,D,H,W], fp32, contiguous, on a HIP device."""
 
     def __init__(self, *args, **kwargs):
@@ -222,6 +287,8 @@ class DiffConv3d(nn.Conv3d):
         with torch.cuda.device(x.device):
             if self.stride[0] == 2:
                 return _StridedFn.apply(x, self.weight, 3, self._packed, False)
+            if self.in_channels != self.out_channels:
+                return _EndFn.apply(x, self.weight, self._packed)
             return _ConvFn.apply(x, self.weight, 3, self._packed)
 
 

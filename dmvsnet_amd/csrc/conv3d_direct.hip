@@ -538,3 +538,6 @@ extern "C" int dmvs_conv3d_direct(const float* in, float* out, const float* w_pa
 
 // K5: train- and eval-mode BatchNorm + ReLU, forward and backward (device code, launchers and its five C entries)
 #include "batchnorm.h"
+
+// K2g: weight gradient of the 2-channel ends conv0 / prob (device code, launcher and its three C entries)
+#include "conv3d_wgrad_c2.h"

@@ -948,6 +948,83 @@ def conv3d_wgrad(x: torch.Tensor, gy: torch.Tensor, kdepth: int, out: Optional[t
     return out
 
 
+# ------------------------------------------------------------------------------------------ K2g (training: the 2-channel ends conv0 / prob)
+WGRAD_C2_TILE = (1, 4, 64)          # voxel tile (z, y, x) of K2g: dmvs_conv3d_wgrad_c2_plan counts these (csrc/conv3d_wgrad_c2.h)
+WGRAD_C2_SHAPES = ((2, 8), (8, 2))  # (Cin, Cout): conv0 and prob
+_wgrad_c2_ws_cache: dict = {}
+
+
+def pack_index_direct(cin: int, cout: int, transposed_flipped: bool, device=None) -> torch.Tensor:
+    """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K2's weight packing for a 3x3x3 layer
+    cin -> cout: for a weight ``w`` [cout,cin,3,3,3] ``w.reshape(-1)[index] == pack_direct(w, False).reshape(-1)`` bit for bit (the
+    packing is a pure permutation).  ``transposed_flipped``: the index of ``pack_direct(w.transpose(0, 1).flip(2, 3, 4), False)``
+    instead -- the weight of the layer's data gradient, a cout -> cin layer.  Derived once on the host by packing an iota."""
+    key = ("direct", int(cin), int(cout), bool(transposed_flipped))
+    if device is not None and torch.device(device).type != "cpu":
+        dkey = key + (torch.device(device),)
+        idx = _pack_index_cache.get(dkey)
+        if idx is None:
+            idx = _pack_index_cache[dkey] = pack_index_direct(cin, cout, transposed_flipped).to(device)
+        return idx
+    idx = _pack_index_cache.get(key)
+    if idx is None:
+        n = cin * cout * 27
+        if cin < 1 or cout < 1 or n >= (1 << 24):   # the iota travels as fp32
+            raise _lib.DmvsError(f"pack_index_direct: cin = {cin}, cout = {cout}")
+        iota = torch.arange(n, dtype=torch.float32).reshape(cout, cin, 3, 3, 3)
+        if transposed_flipped:
+            iota = iota.transpose(0, 1).flip(2, 3, 4).contiguous()
+        idx = _pack_index_cache[key] = pack_direct(iota, False).reshape(-1).to(torch.int64)
+    return idx
+
+
+def _wgrad_c2_dims(x: torch.Tensor, gy: torch.Tensor):
+    if x.dim() != 4 or gy.dim() != 4 or x.shape[1:] != gy.shape[1:] or (int(x.shape[0]), int(gy.shape[0])) not in WGRAD_C2_SHAPES:
+        raise _lib.DmvsError(f"conv3d_wgrad_c2: x {tuple(x.shape)} and gy {tuple(gy.shape)} must be [Cin,D,H,W] and [Cout,D,H,W] of one "
+                             f"volume with (Cin, Cout) in {WGRAD_C2_SHAPES}")
+    return (int(x.shape[0]), int(gy.shape[0]), *(int(n) for n in x.shape[1:]))
+
+
+def conv3d_wgrad_c2_workspace(Cin: int, Cout: int, D: int, H: int, W: int, device) -> torch.Tensor:
+    """K2g's workspace, one per (size, device, stream): its size does not depend on the volume."""
+    n = _lib.load().dmvs_conv3d_wgrad_c2_workspace(Cin, Cout, D, H, W)
+    if n <= 0:
+        raise _lib.DmvsError(f"conv3d_wgrad_c2: (Cin, Cout) = {(Cin, Cout)}, volume {(D, H, W)} is not covered by the weight-gradient kernel")
+    dev = torch.device(device)
+    key = (n, dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _wgrad_c2_ws_cache.get(key)
+    if ws is None:
+        ws = _wgrad_c2_ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
+    return ws
+
+
+def conv3d_wgrad_c2(x: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K2g.  x [Cin,D,H,W], gy [Cout,D,H,W] (input of a stride-1 3x3x3 pad-1 conv and the gradient on its output), (Cin, Cout) =
+    (2, 8) (conv0) or (8, 2) (prob) -> the weight gradient [Cout,Cin,3,3,3].  ``out``: buffer to write into; with ``accumulate`` the
+    result is ADDED to it (it must then be given).  ``workspace``: at least dmvs_conv3d_wgrad_c2_workspace floats (default: a cached
+    buffer per device and stream)."""
+    _req(x, gy, out, workspace)
+    Cin, Cout, D, H, W = _wgrad_c2_dims(x, gy)
+    if accumulate and out is None:
+        raise _lib.DmvsError("conv3d_wgrad_c2: accumulate needs the buffer to add to (out)")
+    if out is None:
+        out = torch.empty((Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    elif out.numel() != Cout * Cin * 27:
+        raise _lib.DmvsError(f"conv3d_wgrad_c2: out {tuple(out.shape)} is not a [{Cout},{Cin},3,3,3] weight")
+    if workspace is None:
+        workspace = conv3d_wgrad_c2_workspace(Cin, Cout, D, H, W, x.device)
+    elif workspace.numel() < _lib.load().dmvs_conv3d_wgrad_c2_workspace(Cin, Cout, D, H, W):
+        raise _lib.DmvsError("conv3d_wgrad_c2: workspace too small")
+    cost = None
+    if timer is not None:
+        cost = (2.0 * 27 * Cin * Cout * D * H * W, 4.0 * ((Cin + Cout) * D * H * W + 27 * Cin * Cout), None)
+    _launch(_lib.load().dmvs_conv3d_wgrad_c2, (_ptr(x), _ptr(gy), _ptr(out), _ptr(workspace), Cin, Cout, D, H, W, 1 if accumulate else 0),
+            f"wgrad{Cin}to{Cout}", "wgrad_c2", x, (gy, out, workspace), False, "conv3d_wgrad_c2", cost)
+    _log("conv3d_wgrad_c2")   # two dispatches per call: the partials and their sum (scripts/pmc_summary.py joins by dispatch order)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ K3h (training: the stride-2 and transposed convs)
 # coarse voxel tile (z, y, x) of K3h per (Ca, kdepth): dmvs_conv3d_wgrad_s2_plan counts these (csrc/conv3d_wgrad_s2.h)
 WGRAD_S2_TILE = {(16, 3): (1, 4, 32), (32, 3): (1, 4, 32), (64, 3): (1, 2, 32), (64, 1): (1, 4, 32)}

@@ -561,6 +561,27 @@ long dmvs_conv3d_wgrad_s2_workspace(int Ca, int Dc, int Hc, int Wc, int kdepth);
  * Negative DMVS_E* as dmvs_conv3d_wgrad_s2. */
 int dmvs_conv3d_wgrad_s2_plan(int Ca, int Dc, int Hc, int Wc, int kdepth);
 
+/* K2g: weight gradient of the 2-channel ends of the regularisation U-Nets, conv0 (2 -> 8) and `prob` (8 -> 2), 3x3x3, stride 1, pad 1
+ * (csrc/conv3d_wgrad_c2.h, docs/kernels/K2g_conv_wgrad_c2.md) -- what autograd computes for the weight of the reference's conv0 block
+ * and `prob` (networks/module.py:361, 379, 403, 421).  fp32 VALU, lane = voxel.
+ * (Their forward and data gradient are dmvs_conv3d_direct: each one's data gradient has the other one's shape.)
+ *   x          [Cin][D][H][W]: the layer's input;  gy [Cout][D][H][W]: the gradient on its output
+ *   gw         [Cout][Cin][3][3][3] out (nn.Conv3d layout):
+ *              gw[co][ci][kz][ky][kx] (+)= sum_{z,y,x} gy[co][z][y][x] * x[ci][z+kz-1][y+ky-1][x+kx-1], zero outside the volume
+ *   workspace  dmvs_conv3d_wgrad_c2_workspace(...) floats; partial sums, fully overwritten where read
+ *   accumulate 0: gw is overwritten; 1: the sum is added to gw (a batch runs as its samples one after the other)
+ * (Cin, Cout) in {(2, 8), (8, 2)}, else DMVS_EUNSUPPORTED; null pointers, empty sizes or more than 2^22 tiles: DMVS_EINVAL.  Two launches
+ * (partials, then their sum in a fixed order); no atomics: bitwise reproducible. */
+int dmvs_conv3d_wgrad_c2(const float* x, const float* gy, float* gw, float* workspace, int Cin, int Cout, int D, int H, int W,
+                         int accumulate, dmvs_stream_t stream);
+/* Workspace of dmvs_conv3d_wgrad_c2 in floats: one partial [27][8][2] per voxel share, 256 shares at most -- it does not depend on the
+ * volume.  0 for a shape the kernel is not compiled for. */
+long dmvs_conv3d_wgrad_c2_workspace(int Cin, int Cout, int D, int H, int W);
+/* Host only: the launch dmvs_conv3d_wgrad_c2 will make, as tiles * 512 + workgroups.  tiles = D * ceil(H / 4) * ceil(W / 64) voxel tiles
+ * of 1 x 4 x 64; workgroups = the size of the first launch's grid (a multiple of 8, at most 256); workgroups past min(tiles, 256) exit
+ * at once and own no partial.  Negative DMVS_E* as dmvs_conv3d_wgrad_c2. */
+int dmvs_conv3d_wgrad_c2_plan(int Cin, int Cout, int D, int H, int W);
+
 /* K5: BatchNorm + ReLU of the reference's Conv3d / Deconv3d / Conv2d / Deconv2d blocks (networks/module.py: `self.bn(...)`, then
  * `F.relu(x, inplace=True)`), forward and backward, train and eval mode (csrc/batchnorm.h, docs/kernels/K5_batchnorm_relu.md).
  *   x, y, gy, gx   [B][C][V] fp32, V = D * H * W (2D layers: H * W); the batch is handled inside the kernels
