@@ -44,8 +44,17 @@ The 2-channel ends (kernel 3, stride 1, padding 1, no bias): ``DiffConv3d`` also
   ``Cin == 2`` direct form for 2 -> 8, the weight packed on the device by one gather (``ops.pack_index_direct``);
 * data gradient: the OTHER of those two launches on the weight transposed in (co, ci) and flipped in every tap;
 * weight gradient: K2g (``ops.conv3d_wgrad_c2``), accumulated over the samples in batch order.
+
+In the code: one autograd Function (``_ConvFn``) runs every kind of layer; a ``_Kind`` value per kind (square, stride-2, transposed, ends)
+names the builder of its packed layers (the gather and the ``ConvLayer``), the forms of the weight the forward and the data gradient
+launch, the ``ops.conv3d`` backend and the weight-gradient call with its argument order.  Every packed layer comes through one cache
+lookup (``_cached_layer``; ``_packed_layer*`` name it per kind), and the four classes share their constructor and ``forward``
+(``_DiffConv``, mixed in front of the nn class).
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, Union
 
 import torch
 from torch import nn
@@ -66,137 +75,102 @@ CHANNELS_C2 = ops.WGRAD_C2_SHAPES   # (in, out) of the 2-channel ends K2 and K2g
 launch_counts = {"dgrad": 0, "wgrad": 0}
 
 
-def _packed_layer(cache: dict, weight: torch.Tensor, kdepth: int, transposed_flipped: bool) -> ops.ConvLayer:
-    """The bare K3 layer of ``weight`` ([C,C,kd,3,3] or [C,C,3,3]) or of its transposed-flipped form, from the module's cache."""
+def _cached_layer(cache: dict, slot, weight: torch.Tensor, build, kdepth: int) -> ops.ConvLayer:
+    """The layer ``build(weight, kdepth, slot)`` packs, from the module's ``cache`` under ``slot`` (the form of the weight: see the
+    builders) while the weight's version counter, data pointer and device are those it was built from."""
     key = (weight._version, weight.data_ptr(), weight.device)
-    hit = cache.get(transposed_flipped)
+    hit = cache.get(slot)
     if hit is not None and hit[0] == key and hit[2] is weight:   # (the entry holds the tensor: its address cannot be re-used meanwhile)
         return hit[1]
-    C = weight.shape[0]
-    index = ops.pack_index_mfma(C, kdepth, transposed_flipped, weight.device)
-    packed = torch.index_select(weight.detach().reshape(-1), 0, index)   # one device gather: the packing is a permutation
-    layer = ops.ConvLayer("diffconv%d%s" % (C, "t" if transposed_flipped else ""), ops.CONV_S1, kdepth, C, C, None, packed, None, None,
-                          False)
-    cache[transposed_flipped] = (key, layer, weight)
+    layer = build(weight, kdepth, slot)
+    cache[slot] = (key, layer, weight)
     return layer
 
 
-class _ConvFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, kdepth, cache):
-        xd = x.detach()
-        layer = _packed_layer(cache, weight, kdepth, False)
-        out = torch.empty_like(xd)
-        for b in range(xd.shape[0]):
-            ops.conv3d(xd[b], layer, out=out[b], backend="mfma")
-        ctx.save_for_backward(xd, weight)
-        ctx.kdepth, ctx.cache = kdepth, cache
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors   # (raises if the weight was changed in place since the forward)
-        gy = gy.contiguous()
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            layer = _packed_layer(ctx.cache, weight, ctx.kdepth, True)
-            gx = torch.empty_like(x)
-            for b in range(x.shape[0]):
-                ops.conv3d(gy[b], layer, out=gx[b], backend="mfma")
-                launch_counts["dgrad"] += 1
-        if ctx.needs_input_grad[1]:
-            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-            for b in range(x.shape[0]):
-                ops.conv3d_wgrad(x[b], gy[b], ctx.kdepth, out=gw, accumulate=b > 0)
-                launch_counts["wgrad"] += 1
-        return gx, gw, None, None
+def _build_s1(weight, kdepth, transposed_flipped):
+    C = weight.shape[0]
+    index = ops.pack_index_mfma(C, kdepth, transposed_flipped, weight.device)
+    packed = torch.index_select(weight.detach().reshape(-1), 0, index)   # one device gather: the packing is a permutation
+    return ops.ConvLayer("diffconv%d%s" % (C, "t" if transposed_flipped else ""), ops.CONV_S1, kdepth, C, C, None, packed, None, None, False)
 
 
-def _packed_layer_s2(cache: dict, weight: torch.Tensor, kdepth: int, mode: int) -> ops.ConvLayer:
-    """The bare K3 layer that reads ``weight`` in ``mode``: CONV_S2 takes it as [out][in][k..], DECONV_S2 as [in][out][k..] -- the same
-    tensor either way, so a layer's forward and its data gradient are the two modes.  From the module's cache, keyed as _packed_layer."""
-    key = (weight._version, weight.data_ptr(), weight.device)
-    hit = cache.get(mode)
-    if hit is not None and hit[0] == key and hit[2] is weight:
-        return hit[1]
+def _build_s2(weight, kdepth, mode):
     big, small = weight.shape[0], weight.shape[1]
     cin, cout = (small, big) if mode == ops.CONV_S2 else (big, small)
     index = ops.pack_index_mfma_s2(cin, cout, mode, kdepth, weight.device)
     flat = weight.detach().reshape(-1)
     packed = torch.index_select(torch.cat((flat, flat.new_zeros(1))), 0, index)   # a selection with zeros: the appended slot is the zero
-    layer = ops.ConvLayer("diff%s%dto%d" % ("conv_s2_" if mode == ops.CONV_S2 else "deconv_s2_", cin, cout), mode, kdepth, cin, cout, None,
-                          packed, None, None, False)
-    cache[mode] = (key, layer, weight)
-    return layer
+    return ops.ConvLayer("diff%s%dto%d" % ("conv_s2_" if mode == ops.CONV_S2 else "deconv_s2_", cin, cout), mode, kdepth, cin, cout, None,
+                         packed, None, None, False)
 
 
-class _StridedFn(torch.autograd.Function):
-    """A stride-2 conv (``transposed`` False) or a transposed conv (True).  The weight is [coarse channels][fine channels][k..] in
-    both; the forward of the one is the data gradient of the other."""
+def _build_c2(weight, kdepth, transposed_flipped):
+    cout, cin = weight.shape[0], weight.shape[1]
+    index = ops.pack_index_direct(cin, cout, transposed_flipped, weight.device)
+    packed = torch.index_select(weight.detach().reshape(-1), 0, index)   # one device gather: the packing is a permutation
+    lin, lout = (cout, cin) if transposed_flipped else (cin, cout)
+    return ops.ConvLayer("diffconv%dto%d%s" % (cin, cout, "t" if transposed_flipped else ""), ops.CONV_S1, 3, lin, lout, packed, None, None,
+                         None, False)
 
-    @staticmethod
-    def forward(ctx, x, weight, kdepth, cache, transposed):
-        xd = x.detach()
-        fwd, bwd = (ops.DECONV_S2, ops.CONV_S2) if transposed else (ops.CONV_S2, ops.DECONV_S2)
-        layer = _packed_layer_s2(cache, weight, kdepth, fwd)
-        out = torch.empty((xd.shape[0], layer.cout, *layer.out_shape(*xd.shape[2:])), dtype=torch.float32, device=xd.device)
-        for b in range(xd.shape[0]):
-            ops.conv3d(xd[b], layer, out=out[b], backend="mfma")
-        ctx.save_for_backward(xd, weight)
-        ctx.kdepth, ctx.cache, ctx.transposed, ctx.bwd = kdepth, cache, transposed, bwd
-        return out
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors   # (raises if the weight was changed in place since the forward)
-        gy = gy.contiguous()
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            layer = _packed_layer_s2(ctx.cache, weight, ctx.kdepth, ctx.bwd)
-            gx = torch.empty_like(x)
-            for b in range(x.shape[0]):
-                ops.conv3d(gy[b], layer, out=gx[b], backend="mfma")
-                launch_counts["dgrad"] += 1
-        if ctx.needs_input_grad[1]:
-            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-            for b in range(x.shape[0]):
-                coarse, fine = (x[b], gy[b]) if ctx.transposed else (gy[b], x[b])
-                ops.conv3d_wgrad_s2(coarse, fine, ctx.kdepth, out=gw, accumulate=b > 0)
-                launch_counts["wgrad"] += 1
-        return gx, gw, None, None, None
+def _packed_layer(cache: dict, weight: torch.Tensor, kdepth: int, transposed_flipped: bool) -> ops.ConvLayer:
+    """The bare K3 layer of ``weight`` ([C,C,kd,3,3] or [C,C,3,3]) or of its transposed-flipped form, from the module's cache."""
+    return _cached_layer(cache, transposed_flipped, weight, _build_s1, kdepth)
+
+
+def _packed_layer_s2(cache: dict, weight: torch.Tensor, kdepth: int, mode: int) -> ops.ConvLayer:
+    """The bare K3 layer that reads ``weight`` in ``mode``: CONV_S2 takes it as [out][in][k..], DECONV_S2 as [in][out][k..] -- the same
+    tensor either way, so a layer's forward and its data gradient are the two modes.  From the module's cache, keyed as _packed_layer."""
+    return _cached_layer(cache, mode, weight, _build_s2, kdepth)
 
 
 def _packed_layer_c2(cache: dict, weight: torch.Tensor, transposed_flipped: bool) -> ops.ConvLayer:
     """The bare K2 layer of ``weight`` ([8,2,3,3,3] or [2,8,3,3,3]) or of its transposed-flipped form (a layer out -> in), from the
     module's cache, keyed as _packed_layer."""
-    key = (weight._version, weight.data_ptr(), weight.device)
-    hit = cache.get(transposed_flipped)
-    if hit is not None and hit[0] == key and hit[2] is weight:
-        return hit[1]
-    cout, cin = weight.shape[0], weight.shape[1]
-    index = ops.pack_index_direct(cin, cout, transposed_flipped, weight.device)
-    packed = torch.index_select(weight.detach().reshape(-1), 0, index)   # one device gather: the packing is a permutation
-    lin, lout = (cout, cin) if transposed_flipped else (cin, cout)
-    layer = ops.ConvLayer("diffconv%dto%d%s" % (cin, cout, "t" if transposed_flipped else ""), ops.CONV_S1, 3, lin, lout, packed, None,
-                          None, None, False)
-    cache[transposed_flipped] = (key, layer, weight)
-    return layer
+    return _cached_layer(cache, transposed_flipped, weight, _build_c2, 3)
 
 
-class _EndFn(torch.autograd.Function):
-    """conv0 (2 -> 8) or prob (8 -> 2) on K2: the forward of the one has the shape of the data gradient of the other."""
+def _wgrad_down(x, gy, kdepth, **kw):
+    return ops.conv3d_wgrad_s2(gy, x, kdepth, **kw)   # K3h takes (coarse, fine)
 
+
+def _wgrad_ends(x, gy, kdepth, **kw):
+    return ops.conv3d_wgrad_c2(x, gy, **kw)
+
+
+@dataclass(frozen=True)
+class _Kind:
+    """What tells the four kinds of layer apart behind _ConvFn."""
+    build: Callable          # the builder of its packed layers (_cached_layer)
+    fwd: Union[bool, int]    # the form of the weight the forward launches: the builder's last argument and the cache slot
+    bwd: Union[bool, int]    # ... and the data gradient
+    backend: str             # of ops.conv3d, forward and data gradient
+    wgrad: Callable          # (x, gy, kdepth, out=, accumulate=) -> the weight-gradient launch of one sample
+
+
+_SQUARE = _Kind(_build_s1, False, True, "mfma", ops.conv3d_wgrad)
+# a stride-2 conv and a transposed conv: the weight is [coarse channels][fine channels][k..] in both, and the forward of the one is the
+# data gradient of the other
+_DOWN = _Kind(_build_s2, ops.CONV_S2, ops.DECONV_S2, "mfma", _wgrad_down)
+_UP = _Kind(_build_s2, ops.DECONV_S2, ops.CONV_S2, "mfma", ops.conv3d_wgrad_s2)
+# conv0 (2 -> 8) or prob (8 -> 2) on K2: the forward of the one has the shape of the data gradient of the other
+_ENDS = _Kind(_build_c2, False, True, "direct", _wgrad_ends)
+
+
+class _ConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, cache):
+    def forward(ctx, x, weight, cache, kind):
         xd = x.detach()
-        layer = _packed_layer_c2(cache, weight, False)
-        out = torch.empty((xd.shape[0], layer.cout, *xd.shape[2:]), dtype=torch.float32, device=xd.device)
+        kdepth = 3 if weight.dim() == 5 else 1   # (a 2D layer's samples come as D = 1 volumes)
+        layer = _cached_layer(cache, kind.fwd, weight, kind.build, kdepth)
+        if layer.mode == ops.CONV_S1 and layer.cout == layer.cin:   # a square layer: the output has the input's shape
+            out = torch.empty_like(xd)
+        else:
+            out = xd.new_empty((xd.shape[0], layer.cout, *layer.out_shape(*xd.shape[2:])))
         for b in range(xd.shape[0]):
-            ops.conv3d(xd[b], layer, out=out[b], backend="direct")
+            ops.conv3d(xd[b], layer, out=out[b], backend=kind.backend)
         ctx.save_for_backward(xd, weight)
-        ctx.cache = cache
+        ctx.kdepth, ctx.cache, ctx.kind = kdepth, cache, kind
         return out
 
     @staticmethod
@@ -206,17 +180,17 @@ class _EndFn(torch.autograd.Function):
         gy = gy.contiguous()
         gx = gw = None
         if ctx.needs_input_grad[0]:
-            layer = _packed_layer_c2(ctx.cache, weight, True)
+            layer = _cached_layer(ctx.cache, ctx.kind.bwd, weight, ctx.kind.build, ctx.kdepth)
             gx = torch.empty_like(x)
             for b in range(x.shape[0]):
-                ops.conv3d(gy[b], layer, out=gx[b], backend="direct")
+                ops.conv3d(gy[b], layer, out=gx[b], backend=ctx.kind.backend)
                 launch_counts["dgrad"] += 1
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
             for b in range(x.shape[0]):
-                ops.conv3d_wgrad_c2(x[b], gy[b], out=gw, accumulate=b > 0)
+                ctx.kind.wgrad(x[b], gy[b], ctx.kdepth, out=gw, accumulate=b > 0)
                 launch_counts["wgrad"] += 1
-        return gx, gw, None
+        return gx, gw, None, None
 
 
 def _check_even(what, x, nd):
@@ -225,27 +199,28 @@ def _check_even(what, x, nd):
                         f"layer with output_padding 1, and the U-Net's skip additions need them anyway); got {tuple(x.shape)}")
 
 
+def _ctor_common(nd, m):
+    """Holds for every layer the kernels take: kernel 3, padding 1, dilation 1, groups 1, no bias, zero padding."""
+    return m.kernel_size == (3,) * nd and m.padding == (1,) * nd and m.dilation == (1,) * nd and m.groups == 1 and m.bias is None \
+        and m.padding_mode == "zeros"
+
+
 def _check_ctor_transposed(what, nd, m):
-    one, two, three = (1,) * nd, (2,) * nd, (3,) * nd
     pairs = tuple((co, ci) for ci, co in CHANNELS_S2[nd])
-    if m.kernel_size != three or m.stride != two or m.padding != one or m.output_padding != one or m.dilation != one or m.groups != 1 \
-            or m.bias is not None or m.padding_mode != "zeros" or (m.in_channels, m.out_channels) not in pairs:
+    if not _ctor_common(nd, m) or m.stride != (2,) * nd or m.output_padding != (1,) * nd or (m.in_channels, m.out_channels) not in pairs:
         raise DmvsError(f"{what}: only kernel 3, stride 2, padding 1, output_padding 1, dilation 1, groups 1, bias=False and (in, out) in "
                         f"{pairs} run on the gfx950 kernels (no ATen fallback); got {m}")
 
 
 def _check_ctor(what, nd, m):
-    one, three = (1,) * nd, (3,) * nd
     if m.stride == (2,) * nd:
-        if m.kernel_size != three or m.padding != one or m.dilation != one or m.groups != 1 or m.bias is not None \
-                or m.padding_mode != "zeros" or (m.in_channels, m.out_channels) not in CHANNELS_S2[nd]:
+        if not _ctor_common(nd, m) or (m.in_channels, m.out_channels) not in CHANNELS_S2[nd]:
             raise DmvsError(f"{what}: at stride 2 only kernel 3, padding 1, dilation 1, groups 1, bias=False and (in, out) in "
                             f"{CHANNELS_S2[nd]} run on the gfx950 kernels (no ATen fallback); got {m}")
         return
     square = m.in_channels == m.out_channels and m.in_channels in CHANNELS
     ends = nd == 3 and (m.in_channels, m.out_channels) in CHANNELS_C2
-    if m.kernel_size != three or m.stride != one or m.padding != one or m.dilation != one or m.groups != 1 or m.bias is not None \
-            or m.padding_mode != "zeros" or not (square or ends):
+    if not _ctor_common(nd, m) or m.stride != (1,) * nd or not (square or ends):
         raise DmvsError(f"{what}: only kernel 3, stride 1, padding 1, dilation 1, groups 1, bias=False and in == out in {CHANNELS}"
                         f"{f' or (in, out) in {CHANNELS_C2}' if nd == 3 else ''} run on the gfx950 kernels (no ATen fallback); got {m}")
 
@@ -268,83 +243,66 @@ def _check_weight(what, w, x):
         raise DmvsError(f"{what}: the weight must be contiguous fp32 on the input's device {x.device}; it is {w.dtype} on {w.device}")
 
 
-class DiffConv3d(nn.Conv3d):
+class _DiffConv:
+    """What the four layer classes share (mixed in front of the nn class): the constructor's refusals, the per-module cache of packed
+    weights and the forward.  A 2D layer runs each sample as a D = 1 volume."""
+    _nd, _transposed = 3, False
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        (_check_ctor_transposed if self._transposed else _check_ctor)(type(self).__name__, self._nd, self)
+        self._packed = {}
+
+    def forward(self, x):
+        what, nd, weight = type(self).__name__, self._nd, self.weight
+        # (chosen on every call from what nn.Module copies and pickles, so a copied or reloaded module runs as the one it was made from)
+        down = self.stride[0] == 2 and not self._transposed
+        if self._transposed:
+            kind = _UP
+        elif down:
+            kind = _DOWN
+        else:
+            kind = _SQUARE if self.in_channels == self.out_channels else _ENDS
+        _check_input(what, x, nd, self.in_channels)
+        _check_weight(what, weight, x)
+        if down:
+            _check_even(what, x, nd)
+        with torch.cuda.device(x.device):
+            if nd == 3:
+                return _ConvFn.apply(x, weight, self._packed, kind)
+            return _ConvFn.apply(x.unsqueeze(2), weight, self._packed, kind).squeeze(2)
+
+
+class _DiffConvTranspose(_DiffConv):
+    _transposed = True
+
+    def forward(self, x, output_size=None):
+        if output_size is not None:
+            raise DmvsError(f"{type(self).__name__}: output_size is not supported (the output is twice the input)")
+        return super().forward(x)
+
+
+class DiffConv3d(_DiffConv, nn.Conv3d):
     """``nn.Conv3d(C, C, 3, stride=1, padding=1, bias=False)``, C in {16, 32, 64}, on K3 (forward, data gradient) and K3g (weight
     gradient); or ``nn.Conv3d(C, 2 * C, 3, stride=2, padding=1, bias=False)``, C in {8, 16, 32}, on K3 and K3h (even D, H, W); or
     ``nn.Conv3d(2, 8, 3, stride=1, padding=1, bias=False)`` / ``nn.Conv3d(8, 2, ...)``, conv0 / ``prob``, on K2 and K2g.  Input
     [B,C,D,H,W], fp32, contiguous, on a HIP device."""
 
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        _check_ctor("DiffConv3d", 3, self)
-        self._packed = {}
 
-    def forward(self, x):
-        _check_input("DiffConv3d", x, 3, self.in_channels)
-        _check_weight("DiffConv3d", self.weight, x)
-        if self.stride[0] == 2:
-            _check_even("DiffConv3d", x, 3)
-        with torch.cuda.device(x.device):
-            if self.stride[0] == 2:
-                return _StridedFn.apply(x, self.weight, 3, self._packed, False)
-            if self.in_channels != self.out_channels:
-                return _EndFn.apply(x, self.weight, self._packed)
-            return _ConvFn.apply(x, self.weight, 3, self._packed)
-
-
-class DiffConv2d(nn.Conv2d):
+class DiffConv2d(_DiffConv, nn.Conv2d):
     """``nn.Conv2d(C, C, 3, stride=1, padding=1, bias=False)``, C in {16, 32, 64}, on the kdepth-1 forms of K3 and K3g; or
     ``nn.Conv2d(32, 64, 3, stride=2, padding=1, bias=False)`` on those of K3 and K3h (even H, W).  Input [B,C,H,W], fp32, contiguous, on
     a HIP device; each sample is a D = 1 volume."""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        _check_ctor("DiffConv2d", 2, self)
-        self._packed = {}
-
-    def forward(self, x):
-        _check_input("DiffConv2d", x, 2, self.in_channels)
-        _check_weight("DiffConv2d", self.weight, x)
-        if self.stride[0] == 2:
-            _check_even("DiffConv2d", x, 2)
-        with torch.cuda.device(x.device):
-            if self.stride[0] == 2:
-                return _StridedFn.apply(x.unsqueeze(2), self.weight, 1, self._packed, False).squeeze(2)
-            return _ConvFn.apply(x.unsqueeze(2), self.weight, 1, self._packed).squeeze(2)
+    _nd = 2
 
 
-class DiffConvTranspose3d(nn.ConvTranspose3d):
+class DiffConvTranspose3d(_DiffConvTranspose, nn.ConvTranspose3d):
     """``nn.ConvTranspose3d(2 * C, C, 3, stride=2, padding=1, output_padding=1, bias=False)``, C in {32, 16, 8}, on K3 (forward: the
     transposed launch; data gradient: the stride-2 launch on the same weight) and K3h (weight gradient).  Input [B,2C,D,H,W], fp32,
     contiguous, on a HIP device; output [B,C,2D,2H,2W]."""
 
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        _check_ctor_transposed("DiffConvTranspose3d", 3, self)
-        self._packed = {}
 
-    def forward(self, x, output_size=None):
-        if output_size is not None:
-            raise DmvsError("DiffConvTranspose3d: output_size is not supported (the output is twice the input)")
-        _check_input("DiffConvTranspose3d", x, 3, self.in_channels)
-        _check_weight("DiffConvTranspose3d", self.weight, x)
-        with torch.cuda.device(x.device):
-            return _StridedFn.apply(x, self.weight, 3, self._packed, True)
-
-
-class DiffConvTranspose2d(nn.ConvTranspose2d):
+class DiffConvTranspose2d(_DiffConvTranspose, nn.ConvTranspose2d):
     """``nn.ConvTranspose2d(64, 32, 3, stride=2, padding=1, output_padding=1, bias=False)`` on the kdepth-1 forms of K3 and K3h.  Input
     [B,64,H,W], fp32, contiguous, on a HIP device; output [B,32,2H,2W]."""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        _check_ctor_transposed("DiffConvTranspose2d", 2, self)
-        self._packed = {}
-
-    def forward(self, x, output_size=None):
-        if output_size is not None:
-            raise DmvsError("DiffConvTranspose2d: output_size is not supported (the output is twice the input)")
-        _check_input("DiffConvTranspose2d", x, 2, self.in_channels)
-        _check_weight("DiffConvTranspose2d", self.weight, x)
-        with torch.cuda.device(x.device):
-            return _StridedFn.apply(x.unsqueeze(2), self.weight, 1, self._packed, True).squeeze(2)
+    _nd = 2

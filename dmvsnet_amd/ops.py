@@ -3,6 +3,12 @@ current HIP stream, tensors out.  PyTorch is used for device memory and streams 
 
 Every function requires CUDA(HIP) fp32 contiguous tensors and raises otherwise: there is no CPU path
 in the product (the CPU restatement lives in oracle/ and is test infrastructure).
+
+Every launch that is logged and timed goes through ``_launch``: it checks the devices of the weights, hands the timer's start event
+back when the launch fails, and writes the launch log and the timer record.  The training wrappers share one workspace cache
+(``_workspace``; the four public getters query their size and delegate), one gather-index cache (``_pack_index``; the three
+``pack_index_*`` functions supply the builder).  The three weight-gradient wrappers keep a body each: one body would take eleven
+parameters.
 """
 from __future__ import annotations
 
@@ -162,7 +168,8 @@ def _launch(fn, args, name: str, kernel: str, x: torch.Tensor, weights, decline:
         if decline and code == _lib.EUNSUPPORTED:
             return False
         _lib.check(code, f"{kernel}[{name}]")
-    _log(family)
+    if launch_log is not None:   # (_log, inline: this runs for every launch)
+        launch_log.append(family)
     if t0 is not None:
         timer.end(family, t0, *cost, label=label or name)
     return True
@@ -381,26 +388,24 @@ def warp_corr(ref: torch.Tensor, src: Sequence[torch.Tensor], proj12: torch.Tens
     assert proj12.shape[0] == nsrc
     arr = (ctypes.c_void_p * nsrc)(*[s.data_ptr() for s in src])
     lib = _lib.load()
-    t0 = timer.begin() if timer is not None else None
     if layout == "q4":
-        fn = lib.dmvs_warp_corr_q4_f16 if f16 else lib.dmvs_warp_corr_q4
-        _lib.check(fn(_ptr(ref), arr, nsrc, _ptr(proj12), None if affine else _ptr(depth_dhw),
-                                         _ptr(depth_dhw.base) if affine else None, _ptr(depth_dhw.step) if affine else None,
-                      _ptr(out), C, D, H, W, int(accumulate), int(variant), _stream()), "dmvs_warp_corr_q4")
+        fn, kernel = (lib.dmvs_warp_corr_q4_f16 if f16 else lib.dmvs_warp_corr_q4), "dmvs_warp_corr_q4"
+        args = (_ptr(ref), arr, nsrc, _ptr(proj12), None if affine else _ptr(depth_dhw), _ptr(depth_dhw.base) if affine else None,
+                _ptr(depth_dhw.step) if affine else None, _ptr(out), C, D, H, W, int(accumulate), int(variant))
     elif affine:
-        _lib.check(lib.dmvs_warp_corr_affine(_ptr(ref), arr, nsrc, pix_stride, _ptr(proj12), _ptr(depth_dhw.base),
-                                             _ptr(depth_dhw.step), _ptr(out), C, D, H, W, int(accumulate), _stream()),
-                   "dmvs_warp_corr_affine")
+        fn, kernel = lib.dmvs_warp_corr_affine, "dmvs_warp_corr_affine"
+        args = (_ptr(ref), arr, nsrc, pix_stride, _ptr(proj12), _ptr(depth_dhw.base), _ptr(depth_dhw.step), _ptr(out), C, D, H, W,
+                int(accumulate))
     else:
-        _lib.check(lib.dmvs_warp_corr(_ptr(ref), arr, nsrc, pix_stride, _ptr(proj12), _ptr(depth_dhw),
-                                      _ptr(out), C, D, H, W, int(accumulate), _stream()), "dmvs_warp_corr")
-    _log(family)
-    if t0 is not None:
+        fn, kernel = lib.dmvs_warp_corr, "dmvs_warp_corr"
+        args = (_ptr(ref), arr, nsrc, pix_stride, _ptr(proj12), _ptr(depth_dhw), _ptr(out), C, D, H, W, int(accumulate))
+    cost = None
+    if timer is not None:
         # algorithmic bytes: features once, similarity volume written once, hypotheses once -- the [D,H,W] volume, or
         # only the [H,W] base plane when the affine form is used (count what is actually read)
         hyp = H * W if affine else D * H * W
-        timer.end(family, t0, nsrc * D * H * W * (10.0 * C + 25),
-                  (2.0 if f16 else 4.0) * (nsrc + 1) * C * H * W + 4.0 * (2 * D * H * W + hyp))
+        cost = (nsrc * D * H * W * (10.0 * C + 25), (2.0 if f16 else 4.0) * (nsrc + 1) * C * H * W + 4.0 * (2 * D * H * W + hyp), None)
+    _launch(fn, args, family, kernel, ref, (), False, family, cost)
     return out
 
 
@@ -782,11 +787,9 @@ def depth_select(dsp: torch.Tensor, interval: torch.Tensor, mode: int):
     _, H, W = dsp.shape
     sel = torch.empty((4, H, W) if mode == 0 else (H, W), dtype=torch.float32, device=dsp.device)
     conf = torch.empty((H, W), dtype=torch.float32, device=dsp.device)
-    t0 = timer.begin() if timer is not None else None
-    _lib.check(_lib.load().dmvs_depth_select(_ptr(dsp), _ptr(interval), mode, H, W, _ptr(sel), _ptr(conf), _stream()), "dmvs_depth_select")
-    _log("depth_regress")
-    if t0 is not None:
-        timer.end("depth_regress", t0, 0.0, 4.0 * (4 + (5 if mode == 0 else 2)) * H * W)
+    cost = None if timer is None else (0.0, 4.0 * (4 + (5 if mode == 0 else 2)) * H * W, None)
+    _launch(_lib.load().dmvs_depth_select, (_ptr(dsp), _ptr(interval), mode, H, W, _ptr(sel), _ptr(conf)), "depth_regress",
+            "dmvs_depth_select", dsp, (), False, "depth_regress", cost)
     return sel, conf
 
 
@@ -806,16 +809,15 @@ def depth_regress(logits: torch.Tensor, depth_dhw: torch.Tensor, interval: torch
     sel = torch.empty((4, H, W) if mode == 0 else (H, W), dtype=torch.float32, device=dev)
     conf = torch.empty((H, W), dtype=torch.float32, device=dev)
     prob = torch.empty_like(logits) if want_prob else None
-    t0 = timer.begin() if timer is not None else None
-    fn = _lib.load().dmvs_depth_regress_affine if affine else _lib.load().dmvs_depth_regress
-    _lib.check(fn(_ptr(logits), _ptr(depth_dhw.base if affine else depth_dhw), _ptr(interval), float(alpha), mode, D, H, W,
-                  _ptr(dsp), _ptr(sel), _ptr(conf), _ptr(prob), _stream()), "dmvs_depth_regress")
-    _log("depth_regress")
-    if t0 is not None:
+    cost = None
+    if timer is not None:
         # algorithmic bytes: the 4 logit planes per hypothesis once + the hypotheses ([D,H,W], or only the [H,W] base plane of the
         # affine form -- VERDICT r05: count what is read) + the outputs (dsp 4, sel 4 | 1, conf 1 planes) (+ the softmax volume)
         hyp = H * W if affine else D * H * W
-        timer.end("depth_regress", t0, 0.0, 4.0 * (4 * D * H * W + hyp + (9 if mode == 0 else 6) * H * W + (4 * D * H * W if want_prob else 0)))
+        cost = (0.0, 4.0 * (4 * D * H * W + hyp + (9 if mode == 0 else 6) * H * W + (4 * D * H * W if want_prob else 0)), None)
+    fn = _lib.load().dmvs_depth_regress_affine if affine else _lib.load().dmvs_depth_regress
+    _launch(fn, (_ptr(logits), _ptr(depth_dhw.base if affine else depth_dhw), _ptr(interval), float(alpha), mode, D, H, W, _ptr(dsp),
+                 _ptr(sel), _ptr(conf), _ptr(prob)), "depth_regress", "dmvs_depth_regress", logits, (), False, "depth_regress", cost)
     return dsp, sel, conf, prob
 
 
@@ -836,19 +838,15 @@ def depth_regress_backward(logits: torch.Tensor, hyp_dhw: torch.Tensor, alpha: f
     if want_hyp and g_hyp is None:
         g_hyp = torch.empty_like(hyp_dhw)
     assert g_logits.shape == logits.shape and (g_hyp is None or g_hyp.shape == hyp_dhw.shape)
-    t0 = timer.begin() if timer is not None else None
-    code = _lib.load().dmvs_depth_regress_backward(_ptr(logits), _ptr(hyp_dhw), float(alpha), mode, D, H, W, _ptr(dsp), _ptr(g_dsp),
-                                                   _ptr(g_sel), _ptr(g_logits), _ptr(g_hyp if want_hyp else None), _stream())
-    if code:
-        if t0 is not None:
-            timer.cancel(t0)
-        _lib.check(code, "dmvs_depth_regress_backward")
-    _log("depth_regress")
-    if t0 is not None:
+    cost = None
+    if timer is not None:
         # algorithmic bytes: the logit volume read and its gradient written once (32 N, N = D H W), the hypotheses read (and their
         # gradient written), dsp and the upstream planes
         planes = 4 + (4 if g_dsp is not None else 0) + (0 if g_sel is None else (4 if mode == 0 else 1))
-        timer.end("depth_regress", t0, 0.0, 4.0 * (8 * D * H * W + (2 if want_hyp else 1) * D * H * W + planes * H * W))
+        cost = (0.0, 4.0 * (8 * D * H * W + (2 if want_hyp else 1) * D * H * W + planes * H * W), None)
+    _launch(_lib.load().dmvs_depth_regress_backward,
+            (_ptr(logits), _ptr(hyp_dhw), float(alpha), mode, D, H, W, _ptr(dsp), _ptr(g_dsp), _ptr(g_sel), _ptr(g_logits),
+             _ptr(g_hyp if want_hyp else None)), "depth_regress", "dmvs_depth_regress_backward", logits, (), False, "depth_regress", cost)
     return g_logits, (g_hyp if want_hyp else None)
 
 
@@ -870,10 +868,40 @@ def dual_depth_loss_backward(dsp_main: torch.Tensor, dsp_refine: torch.Tensor, g
     return g_main, g_refine
 
 
+# ------------------------------------------------------------------------------------------ training: shared by K3g / K3h / K2g / K5
+_pack_index_cache: dict = {}
+_ws_cache: dict = {}
+
+
+def _pack_index(key: tuple, build: Callable[[], torch.Tensor], device) -> torch.Tensor:
+    """The gather index ``key`` of the pack_index_* functions from their one cache: the host LongTensor, derived and validated once by
+    ``build()``, or its copy on ``device``, made once per device.  Repeated calls return the same tensor object."""
+    if device is not None and torch.device(device).type != "cpu":
+        dkey = key + (torch.device(device),)
+        idx = _pack_index_cache.get(dkey)
+        if idx is None:
+            idx = _pack_index_cache[dkey] = _pack_index(key, build, None).to(device)
+        return idx
+    idx = _pack_index_cache.get(key)
+    if idx is None:
+        idx = _pack_index_cache[key] = build()
+    return idx
+
+
+def _workspace(kind: str, n: int, device) -> torch.Tensor:
+    """The cached workspace of ``n`` floats of the kernel family ``kind``, one per (kind, size, device, stream)."""
+    dev = torch.device(device)
+    if dev.index is None:   # "cuda" and "cuda:<current>" are one device and must be one workspace
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    key = (kind, n, dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _ws_cache.get(key)
+    if ws is None:
+        ws = _ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
+    return ws
+
+
 # ------------------------------------------------------------------------------------------ K3g (training: the stride-1 square convs)
 WGRAD_TILE = (1, 4, 32)   # voxel tile (z, y, x) of K3g: dmvs_conv3d_wgrad_plan counts these (csrc/conv3d_wgrad.h)
-_pack_index_cache: dict = {}
-_wgrad_ws_cache: dict = {}
 
 
 def pack_index_mfma(C: int, kdepth: int, transposed_flipped: bool, device=None) -> torch.Tensor:
@@ -882,15 +910,7 @@ def pack_index_mfma(C: int, kdepth: int, transposed_flipped: bool, device=None) 
     bit (the packing of these shapes is a pure permutation).  ``transposed_flipped``: the index of
     ``pack_mfma(w.transpose(0, 1).flip(2, 3, 4), ...)`` instead -- the weight of the layer's data gradient.  Derived once on the host
     by packing an iota through the library's packer."""
-    key = (int(C), int(kdepth), bool(transposed_flipped))
-    if device is not None and torch.device(device).type != "cpu":
-        dkey = key + (torch.device(device),)
-        idx = _pack_index_cache.get(dkey)
-        if idx is None:
-            idx = _pack_index_cache[dkey] = pack_index_mfma(C, kdepth, transposed_flipped).to(device)
-        return idx
-    idx = _pack_index_cache.get(key)
-    if idx is None:
+    def build():
         n = C * C * 9 * kdepth
         if kdepth not in (1, 3) or n >= (1 << 24):   # the iota travels as fp32
             raise _lib.DmvsError(f"pack_index_mfma: C = {C}, kdepth = {kdepth}")
@@ -903,8 +923,8 @@ def pack_index_mfma(C: int, kdepth: int, transposed_flipped: bool, device=None) 
         idx = packed.to(torch.int64)
         if idx.numel() != n or not torch.equal(torch.sort(idx).values, torch.arange(n)):
             raise _lib.DmvsError(f"pack_index_mfma: the packing of {C} -> {C}, kdepth {kdepth} is not a permutation")
-        _pack_index_cache[key] = idx
-    return idx
+        return idx
+    return _pack_index((int(C), int(kdepth), bool(transposed_flipped)), build, device)
 
 
 def conv3d_wgrad_workspace(C: int, D: int, H: int, W: int, kdepth: int, device) -> torch.Tensor:
@@ -912,12 +932,7 @@ def conv3d_wgrad_workspace(C: int, D: int, H: int, W: int, kdepth: int, device) 
     n = _lib.load().dmvs_conv3d_wgrad_workspace(C, D, H, W, kdepth)
     if n <= 0:
         raise _lib.DmvsError(f"conv3d_wgrad: C = {C}, kdepth = {kdepth}, volume {(D, H, W)} is not covered by the weight-gradient kernel")
-    dev = torch.device(device)
-    key = (n, dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _wgrad_ws_cache.get(key)
-    if ws is None:
-        ws = _wgrad_ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
-    return ws
+    return _workspace("k3g", n, device)
 
 
 def conv3d_wgrad(x: torch.Tensor, gy: torch.Tensor, kdepth: int, out: Optional[torch.Tensor] = None, accumulate: bool = False,
@@ -951,7 +966,6 @@ def conv3d_wgrad(x: torch.Tensor, gy: torch.Tensor, kdepth: int, out: Optional[t
 # ------------------------------------------------------------------------------------------ K2g (training: the 2-channel ends conv0 / prob)
 WGRAD_C2_TILE = (1, 4, 64)          # voxel tile (z, y, x) of K2g: dmvs_conv3d_wgrad_c2_plan counts these (csrc/conv3d_wgrad_c2.h)
 WGRAD_C2_SHAPES = ((2, 8), (8, 2))  # (Cin, Cout): conv0 and prob
-_wgrad_c2_ws_cache: dict = {}
 
 
 def pack_index_direct(cin: int, cout: int, transposed_flipped: bool, device=None) -> torch.Tensor:
@@ -959,23 +973,15 @@ def pack_index_direct(cin: int, cout: int, transposed_flipped: bool, device=None
     cin -> cout: for a weight ``w`` [cout,cin,3,3,3] ``w.reshape(-1)[index] == pack_direct(w, False).reshape(-1)`` bit for bit (the
     packing is a pure permutation).  ``transposed_flipped``: the index of ``pack_direct(w.transpose(0, 1).flip(2, 3, 4), False)``
     instead -- the weight of the layer's data gradient, a cout -> cin layer.  Derived once on the host by packing an iota."""
-    key = ("direct", int(cin), int(cout), bool(transposed_flipped))
-    if device is not None and torch.device(device).type != "cpu":
-        dkey = key + (torch.device(device),)
-        idx = _pack_index_cache.get(dkey)
-        if idx is None:
-            idx = _pack_index_cache[dkey] = pack_index_direct(cin, cout, transposed_flipped).to(device)
-        return idx
-    idx = _pack_index_cache.get(key)
-    if idx is None:
+    def build():
         n = cin * cout * 27
         if cin < 1 or cout < 1 or n >= (1 << 24):   # the iota travels as fp32
             raise _lib.DmvsError(f"pack_index_direct: cin = {cin}, cout = {cout}")
         iota = torch.arange(n, dtype=torch.float32).reshape(cout, cin, 3, 3, 3)
         if transposed_flipped:
             iota = iota.transpose(0, 1).flip(2, 3, 4).contiguous()
-        idx = _pack_index_cache[key] = pack_direct(iota, False).reshape(-1).to(torch.int64)
-    return idx
+        return pack_direct(iota, False).reshape(-1).to(torch.int64)
+    return _pack_index(("direct", int(cin), int(cout), bool(transposed_flipped)), build, device)
 
 
 def _wgrad_c2_dims(x: torch.Tensor, gy: torch.Tensor):
@@ -990,12 +996,7 @@ def conv3d_wgrad_c2_workspace(Cin: int, Cout: int, D: int, H: int, W: int, devic
     n = _lib.load().dmvs_conv3d_wgrad_c2_workspace(Cin, Cout, D, H, W)
     if n <= 0:
         raise _lib.DmvsError(f"conv3d_wgrad_c2: (Cin, Cout) = {(Cin, Cout)}, volume {(D, H, W)} is not covered by the weight-gradient kernel")
-    dev = torch.device(device)
-    key = (n, dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _wgrad_c2_ws_cache.get(key)
-    if ws is None:
-        ws = _wgrad_c2_ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
-    return ws
+    return _workspace("k2g", n, device)
 
 
 def conv3d_wgrad_c2(x: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False,
@@ -1028,7 +1029,6 @@ def conv3d_wgrad_c2(x: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Tenso
 # ------------------------------------------------------------------------------------------ K3h (training: the stride-2 and transposed convs)
 # coarse voxel tile (z, y, x) of K3h per (Ca, kdepth): dmvs_conv3d_wgrad_s2_plan counts these (csrc/conv3d_wgrad_s2.h)
 WGRAD_S2_TILE = {(16, 3): (1, 4, 32), (32, 3): (1, 4, 32), (64, 3): (1, 2, 32), (64, 1): (1, 4, 32)}
-_wgrad_s2_ws_cache: dict = {}
 
 
 def pack_index_mfma_s2(cin: int, cout: int, mode: int, kdepth: int, device=None) -> torch.Tensor:
@@ -1038,15 +1038,7 @@ def pack_index_mfma_s2(cin: int, cout: int, mode: int, kdepth: int, device=None)
     packings are selections with zeros, not permutations (conv1's packed-K form pads its last k-step, conv11's y-parity-merged form has
     zero rows): a zero of the packed form selects the one appended zero slot, index n = cin * cout * 9 * kdepth.  Derived once on the
     host by packing ``iota + 1`` through the library's packer; every weight element must be selected exactly once."""
-    key = ("s2", int(cin), int(cout), int(mode), int(kdepth))
-    if device is not None and torch.device(device).type != "cpu":
-        dkey = key + (torch.device(device),)
-        idx = _pack_index_cache.get(dkey)
-        if idx is None:
-            idx = _pack_index_cache[dkey] = pack_index_mfma_s2(cin, cout, mode, kdepth).to(device)
-        return idx
-    idx = _pack_index_cache.get(key)
-    if idx is None:
+    def build():
         n = cin * cout * 9 * kdepth
         ok = (mode == CONV_S2 and cout == 2 * cin) or (mode == DECONV_S2 and cin == 2 * cout)
         if not ok or kdepth not in (1, 3) or n < 1 or n + 1 >= (1 << 24):   # the iota travels as fp32
@@ -1061,8 +1053,8 @@ def pack_index_mfma_s2(cin: int, cout: int, mode: int, kdepth: int, device=None)
         if not torch.equal(torch.bincount(idx, minlength=n + 1)[:n], torch.ones(n, dtype=torch.int64)):
             raise _lib.DmvsError(f"pack_index_mfma_s2: the packing of {cin} -> {cout}, mode {mode}, kdepth {kdepth} does not select every "
                                  "weight element exactly once")
-        _pack_index_cache[key] = idx
-    return idx
+        return idx
+    return _pack_index(("s2", int(cin), int(cout), int(mode), int(kdepth)), build, device)
 
 
 def _wgrad_s2_dims(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int):
@@ -1082,12 +1074,7 @@ def conv3d_wgrad_s2_workspace(Ca: int, Dc: int, Hc: int, Wc: int, kdepth: int, d
     if n <= 0:
         raise _lib.DmvsError(f"conv3d_wgrad_s2: Ca = {Ca}, kdepth = {kdepth}, coarse volume {(Dc, Hc, Wc)} is not covered by the strided "
                              "weight-gradient kernel")
-    dev = torch.device(device)
-    key = (n, dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _wgrad_s2_ws_cache.get(key)
-    if ws is None:
-        ws = _wgrad_s2_ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
-    return ws
+    return _workspace("k3h", n, device)
 
 
 def conv3d_wgrad_s2(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int, out: Optional[torch.Tensor] = None, accumulate: bool = False,
@@ -1125,7 +1112,6 @@ BN_CHANNELS = (8, 16, 32, 64)   # the channel counts K5 takes (csrc/batchnorm.h)
 BN_CHUNK = 1024                 # elements of a chunk: 256 lanes x 4 floats; a share is a run of whole chunks
 BN_MAX_WG = 2048                # workgroups of a launch at most: Smax = BN_MAX_WG // C shares per channel
 BN_TRAIN = 32                   # include/dmvs.h DMVS_BN_TRAIN
-_bn_ws_cache: dict = {}
 
 
 def _bn_dims(x: torch.Tensor):
@@ -1158,14 +1144,7 @@ def bn_workspace(C: int, B: int, V: int, device) -> torch.Tensor:
     n = _lib.load().dmvs_bn_workspace(C, B, V)
     if n <= 0:
         raise _lib.DmvsError(f"bn_relu: C = {C}, B = {B}, V = {V} is not covered by the BatchNorm kernels (C in {BN_CHANNELS})")
-    dev = torch.device(device)
-    if dev.index is None:   # "cuda" and "cuda:<current>" are one device and must be one workspace
-        dev = torch.device(dev.type, torch.cuda.current_device())
-    key = (n, dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _bn_ws_cache.get(key)
-    if ws is None:
-        ws = _bn_ws_cache[key] = torch.empty(n, dtype=torch.float32, device=dev)
-    return ws
+    return _workspace("k5", n, device)
 
 
 def _bn_vectors(what: str, C: int, x: torch.Tensor, *vs: torch.Tensor) -> None:
