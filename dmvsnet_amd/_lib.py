@@ -94,6 +94,10 @@ SIGNATURES = {
     "dmvs_conv3d_wgrad_s2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dmvs_conv3d_wgrad_s2_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i]),
     "dmvs_conv3d_wgrad_s2_plan": (_i, [_i, _i, _i, _i, _i]),
+    "dmvs_conv2d_k5s2_wgrad": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "dmvs_conv2d_k5s2_wgrad_workspace": (ctypes.c_long, [_i, _i, _i, _i]),
+    "dmvs_conv2d_k5s2_wgrad_plan": (_i, [_i, _i, _i, _i]),
+    "dmvs_conv2d_k5s2_dgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "dmvs_conv3d_wgrad_c2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dmvs_conv3d_wgrad_c2_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i]),
     "dmvs_conv3d_wgrad_c2_plan": (_i, [_i, _i, _i, _i, _i]),

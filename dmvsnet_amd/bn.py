@@ -27,7 +27,8 @@ raises in the constructor: there is no ATen fallback.  fp32, contiguous, on a HI
 arguments and have their children (``.conv``, ``.bn``) and state-dict keys; each is a ``DiffConv*`` / ``DiffConvTranspose*`` layer and a
 ``DiffBatchNormReLU*``.  ``bn=False`` or a layer shape the convolution classes refuse raises.  ``DiffConvBlock3d(2, 8, 3, padding=1)`` is
 conv0 as the reference builds it; ``prob`` has no BatchNorm and is a bare ``DiffConv3d(8, 2, ...)`` (``dmvsnet_amd.regnet`` builds the
-whole networks).
+whole networks).  ``DiffConvBlock2d(8, 16, 5, stride=2, padding=2)`` and ``(16, 32, 5, stride=2, padding=2)`` are FeatureNet's conv1.0 /
+conv2.0 (networks/module.py:289, :295) on K3, K3d, K3k and K5.
 """
 from __future__ import annotations
 

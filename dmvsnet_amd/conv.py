@@ -1,7 +1,7 @@
 """Differentiable convolutions of the regularisation U-Nets and FeatureNet behind torch.autograd: the stride-1 square layers (K3 forward
 and data gradient, K3g weight gradient), the stride-2 / transposed layers between them (K3 in both stride-2 modes, K3h weight
-gradient; second part of this text) and the U-Nets' 2-channel ends conv0 / ``prob`` (K2 forward and data gradient, K2g weight gradient;
-third part).
+gradient; second part of this text), the U-Nets' 2-channel ends conv0 / ``prob`` (K2 forward and data gradient, K2g weight gradient;
+third part) and FeatureNet's 5x5 stride-2 layers conv1.0 / conv2.0 (K3 forward, K3d data gradient, K3k weight gradient; fourth part).
 
 ``DiffConv3d`` / ``DiffConv2d`` are ``nn.Conv3d`` / ``nn.Conv2d`` with another ``forward``: parameter name, shape, state-dict layout and
 ``isinstance(m, nn.Conv3d)`` initialisers are the reference's.  A reference user swaps the constructor inside the reference's blocks
@@ -11,7 +11,7 @@ third part).
 
 Accepted at stride 1: kernel 3, padding 1, dilation 1, groups 1, no bias, in == out in {16, 32, 64} -- conv2 / conv4 / conv6 of
 CostRegNet_part, conv2 / conv4 and the 2D conv6 of CostRegNet_part_refine, conv1.1 / 1.2 / 2.1 / 2.2 and out2 of FeatureNet.  Everything
-else raises in the constructor: there is no ATen fallback.  FeatureNet's 5x5 stride-2 and 1x1 layers stay on ATen
+else raises in the constructor: there is no ATen fallback.  FeatureNet's 1x1 layers, conv0.0 / conv0.1 and out3 stay on ATen
 (``dmvsnet_amd.MVSNet.train()`` still raises); BatchNorm + ReLU run on K5 (``dmvsnet_amd.bn``: ``DiffBatchNormReLU3d`` / ``2d``, and the
 blocks ``DiffConvBlock3d`` ... that pair these layers with it); ``dmvsnet_amd.regnet`` builds the four regularisation networks.
 
@@ -45,16 +45,25 @@ The 2-channel ends (kernel 3, stride 1, padding 1, no bias): ``DiffConv3d`` also
 * data gradient: the OTHER of those two launches on the weight transposed in (co, ci) and flipped in every tap;
 * weight gradient: K2g (``ops.conv3d_wgrad_c2``), accumulated over the samples in batch order.
 
-In the code: one autograd Function (``_ConvFn``) runs every kind of layer; a ``_Kind`` value per kind (square, stride-2, transposed, ends)
-names the builder of its packed layers (the gather and the ``ConvLayer``), the forms of the weight the forward and the data gradient
-launch, the ``ops.conv3d`` backend and the weight-gradient call with its argument order.  Every packed layer comes through one cache
+The 5x5 stride-2 layers (kernel 5, stride 2, padding 2, no bias; 2D only): ``DiffConv2d`` also takes (in, out) = (8, 16) and (16, 32) --
+FeatureNet's conv1.0 / conv2.0 (networks/module.py:289, :295).  Even and odd H, W: the output is (H + 1) // 2 x (W + 1) // 2.
+
+* forward: K3's ``CONV2D_K5S2`` launch on the weight packed by one gather (``ops.pack_index_mfma_k5s2``), bit for bit;
+* data gradient: K3d (``ops.conv2d_k5s2_dgrad``), a gather over the four parity classes of the input pixels on the RAW weight -- K3 has
+  no transposed 5x5 form, and nothing is packed or cached for this direction;
+* weight gradient: K3k (``ops.conv2d_k5s2_wgrad``), accumulated over the samples in batch order.
+
+In the code: one autograd Function (``_ConvFn``) runs every kind of layer; a ``_Kind`` value per kind (square, stride-2, transposed, ends,
+5x5) names the builder of its packed layers (the gather and the ``ConvLayer``), the forms of the weight the forward and the data gradient
+launch, the ``ops.conv3d`` backend, the weight-gradient call with its argument order and, for the 5x5 kind, the data-gradient call that
+stands in for the ``ops.conv3d`` launch.  Every packed layer comes through one cache
 lookup (``_cached_layer``; ``_packed_layer*`` name it per kind), and the four classes share their constructor and ``forward``
 (``_DiffConv``, mixed in front of the nn class).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, Union
+from typing import Callable, Optional, Union
 
 import torch
 from torch import nn
@@ -64,12 +73,13 @@ from . import ops
 from ._lib import DmvsError
 
 __all__ = ["DiffConv3d", "DiffConv2d", "DiffConvTranspose3d", "DiffConvTranspose2d", "launch_counts", "CHANNELS", "CHANNELS_S2",
-           "CHANNELS_C2"]
+           "CHANNELS_C2", "CHANNELS_K5S2"]
 
 CHANNELS = (16, 32, 64)   # the square shapes K3 and K3g compile
 # (fine, coarse) channels of the stride-2 / transposed layers K3 and K3h compile, per number of spatial dimensions
 CHANNELS_S2 = {3: ((8, 16), (16, 32), (32, 64)), 2: ((32, 64),)}
 CHANNELS_C2 = ops.WGRAD_C2_SHAPES   # (in, out) of the 2-channel ends K2 and K2g run: conv0 and prob (3D only)
+CHANNELS_K5S2 = ((8, 16), (16, 32))  # (in, out) of the 5x5 stride-2 layers K3, K3k and K3d run: FeatureNet's conv1.0 and conv2.0 (2D only)
 
 # launches of the two backward paths since import (tests check through them that frozen inputs skip their kernel)
 launch_counts = {"dgrad": 0, "wgrad": 0}
@@ -138,14 +148,31 @@ def _wgrad_ends(x, gy, kdepth, **kw):
     return ops.conv3d_wgrad_c2(x, gy, **kw)
 
 
+def _build_k5(weight, kdepth, slot):
+    cout, cin = weight.shape[0], weight.shape[1]
+    index = ops.pack_index_mfma_k5s2(cin, cout, weight.device)
+    flat = weight.detach().reshape(-1)
+    packed = torch.index_select(torch.cat((flat, flat.new_zeros(1))), 0, index)   # a selection with zeros, as _build_s2
+    return ops.ConvLayer("diffconv_k5s2_%dto%d" % (cin, cout), ops.CONV2D_K5S2, 1, cin, cout, None, packed, None, None, False)
+
+
+def _wgrad_k5(x, gy, kdepth, **kw):
+    return ops.conv2d_k5s2_wgrad(x, gy, **kw)
+
+
+def _dgrad_k5(gy, weight, x, out):
+    return ops.conv2d_k5s2_dgrad(gy, weight, x.shape[-2:], out=out)   # K3d reads the raw weight: no packed layer
+
+
 @dataclass(frozen=True)
 class _Kind:
-    """What tells the four kinds of layer apart behind _ConvFn."""
+    """What tells the five kinds of layer apart behind _ConvFn."""
     build: Callable          # the builder of its packed layers (_cached_layer)
     fwd: Union[bool, int]    # the form of the weight the forward launches: the builder's last argument and the cache slot
     bwd: Union[bool, int]    # ... and the data gradient
     backend: str             # of ops.conv3d, forward and data gradient
     wgrad: Callable          # (x, gy, kdepth, out=, accumulate=) -> the weight-gradient launch of one sample
+    dgrad: Optional[Callable] = None   # (gy, weight, x, out) -> the data-gradient launch of one sample, in place of ops.conv3d on `bwd`
 
 
 _SQUARE = _Kind(_build_s1, False, True, "mfma", ops.conv3d_wgrad)
@@ -155,6 +182,8 @@ _DOWN = _Kind(_build_s2, ops.CONV_S2, ops.DECONV_S2, "mfma", _wgrad_down)
 _UP = _Kind(_build_s2, ops.DECONV_S2, ops.CONV_S2, "mfma", ops.conv3d_wgrad_s2)
 # conv0 (2 -> 8) or prob (8 -> 2) on K2: the forward of the one has the shape of the data gradient of the other
 _ENDS = _Kind(_build_c2, False, True, "direct", _wgrad_ends)
+# FeatureNet's 5x5 stride-2 layers: K3's CONV2D_K5S2 forward; no K3 launch has the data gradient's shape, K3d has it on the raw weight
+_DOWN5 = _Kind(_build_k5, ops.CONV2D_K5S2, None, "mfma", _wgrad_k5, _dgrad_k5)
 
 
 class _ConvFn(torch.autograd.Function):
@@ -180,10 +209,14 @@ class _ConvFn(torch.autograd.Function):
         gy = gy.contiguous()
         gx = gw = None
         if ctx.needs_input_grad[0]:
-            layer = _cached_layer(ctx.cache, ctx.kind.bwd, weight, ctx.kind.build, ctx.kdepth)
             gx = torch.empty_like(x)
+            if ctx.kind.dgrad is None:
+                layer = _cached_layer(ctx.cache, ctx.kind.bwd, weight, ctx.kind.build, ctx.kdepth)
             for b in range(x.shape[0]):
-                ops.conv3d(gy[b], layer, out=gx[b], backend=ctx.kind.backend)
+                if ctx.kind.dgrad is None:
+                    ops.conv3d(gy[b], layer, out=gx[b], backend=ctx.kind.backend)
+                else:
+                    ctx.kind.dgrad(gy[b], weight.detach(), x[b], gx[b])
                 launch_counts["dgrad"] += 1
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
@@ -213,6 +246,12 @@ def _check_ctor_transposed(what, nd, m):
 
 
 def _check_ctor(what, nd, m):
+    if nd == 2 and m.kernel_size == (5, 5):
+        if m.stride != (2, 2) or m.padding != (2, 2) or m.dilation != (1, 1) or m.groups != 1 or m.bias is not None \
+                or m.padding_mode != "zeros" or (m.in_channels, m.out_channels) not in CHANNELS_K5S2:
+            raise DmvsError(f"{what}: at kernel 5 only stride 2, padding 2, dilation 1, groups 1, bias=False and (in, out) in "
+                            f"{CHANNELS_K5S2} run on the gfx950 kernels (no ATen fallback); got {m}")
+        return
     if m.stride == (2,) * nd:
         if not _ctor_common(nd, m) or (m.in_channels, m.out_channels) not in CHANNELS_S2[nd]:
             raise DmvsError(f"{what}: at stride 2 only kernel 3, padding 1, dilation 1, groups 1, bias=False and (in, out) in "
@@ -256,9 +295,12 @@ class _DiffConv:
     def forward(self, x):
         what, nd, weight = type(self).__name__, self._nd, self.weight
         # (chosen on every call from what nn.Module copies and pickles, so a copied or reloaded module runs as the one it was made from)
-        down = self.stride[0] == 2 and not self._transposed
+        k5 = self.kernel_size[0] == 5   # (odd extents too: K3d writes the fine tensor the forward read)
+        down = self.stride[0] == 2 and not self._transposed and not k5
         if self._transposed:
             kind = _UP
+        elif k5:
+            kind = _DOWN5
         elif down:
             kind = _DOWN
         else:
@@ -291,8 +333,9 @@ class DiffConv3d(_DiffConv, nn.Conv3d):
 
 class DiffConv2d(_DiffConv, nn.Conv2d):
     """``nn.Conv2d(C, C, 3, stride=1, padding=1, bias=False)``, C in {16, 32, 64}, on the kdepth-1 forms of K3 and K3g; or
-    ``nn.Conv2d(32, 64, 3, stride=2, padding=1, bias=False)`` on those of K3 and K3h (even H, W).  Input [B,C,H,W], fp32, contiguous, on
-    a HIP device; each sample is a D = 1 volume."""
+    ``nn.Conv2d(32, 64, 3, stride=2, padding=1, bias=False)`` on those of K3 and K3h (even H, W); or
+    ``nn.Conv2d(C, 2 * C, 5, stride=2, padding=2, bias=False)``, C in {8, 16}, on K3, K3d and K3k (any H, W).  Input [B,C,H,W], fp32,
+    contiguous, on a HIP device; each sample is a D = 1 volume."""
     _nd = 2
 
 

@@ -541,3 +541,6 @@ extern "C" int dmvs_conv3d_direct(const float* in, float* out, const float* w_pa
 
 // K2g: weight gradient of the 2-channel ends conv0 / prob (device code, launcher and its three C entries)
 #include "conv3d_wgrad_c2.h"
+
+// K3k / K3d: weight and data gradient of FeatureNet's 5x5 stride-2 layers (device code, launchers and its four C entries)
+#include "conv2d_k5s2_bwd.h"

@@ -1107,6 +1107,106 @@ def conv3d_wgrad_s2(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int, out: 
     return out
 
 
+# ------------------------------------------------------------------------------------------ K3k / K3d (training: FeatureNet's 5x5 stride-2 convs)
+WGRAD_K5S2_TILE = (1, 4, 32)             # coarse tile (plane, y, x) of K3k: dmvs_conv2d_k5s2_wgrad_plan counts these (csrc/conv2d_k5s2_bwd.h)
+WGRAD_K5S2_SHAPES = ((8, 16), (16, 32))  # (Cin, Cout): conv1.0 and conv2.0
+
+
+def pack_index_mfma_k5s2(cin: int, cout: int, device=None) -> torch.Tensor:
+    """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K3's weight packing for a 5x5 stride-2 layer
+    (CONV2D_K5S2, weight [cout][cin][5][5], cout = 2 cin): ``torch.cat((w.reshape(-1), zeros(1)))[index] ==
+    pack_mfma(w, cin, cout, CONV2D_K5S2, 1)`` bit for bit.  A zero of the packed form (conv1.0's packed-K form may pad) selects the one
+    appended zero slot, index n = cin * cout * 25.  Derived once on the host by packing ``iota + 1`` through the library's packer;
+    every weight element must be selected exactly once."""
+    def build():
+        n = cin * cout * 25
+        if (cin, cout) not in WGRAD_K5S2_SHAPES:
+            raise _lib.DmvsError(f"pack_index_mfma_k5s2: {cin} -> {cout} is no 5x5 stride-2 layer of FeatureNet {WGRAD_K5S2_SHAPES}")
+        iota = (torch.arange(n, dtype=torch.float32) + 1.0).reshape(cout, cin, 5, 5)   # (n + 1 < 2^24: the iota travels as fp32)
+        packed = pack_mfma(iota, cin, cout, CONV2D_K5S2, 1)
+        if packed is None:
+            raise _lib.DmvsError(f"pack_index_mfma_k5s2: K3 does not compile the 5x5 stride-2 layer {cin} -> {cout}")
+        idx = packed.to(torch.int64) - 1
+        idx[idx < 0] = n
+        if not torch.equal(torch.bincount(idx, minlength=n + 1)[:n], torch.ones(n, dtype=torch.int64)):
+            raise _lib.DmvsError(f"pack_index_mfma_k5s2: the packing of {cin} -> {cout} does not select every weight element exactly once")
+        return idx
+    return _pack_index(("k5s2", int(cin), int(cout)), build, device)
+
+
+def _k5s2_dims(what: str, gy: torch.Tensor, fine_shape):
+    """(Ca, D, Hf, Wf) of a coarse tensor [Ca,D,Hc,Wc] and the shape [Ca/2,D,Hf,Wf] of its fine one."""
+    if gy.dim() != 4 or len(fine_shape) != 4:
+        raise _lib.DmvsError(f"{what}: gy {tuple(gy.shape)} and the fine tensor {tuple(fine_shape)} must be [C,D,H,W]")
+    Ca, D, Hc, Wc = (int(n) for n in gy.shape)
+    Cb, Df, Hf, Wf = (int(n) for n in fine_shape)
+    if (Cb, Ca) not in WGRAD_K5S2_SHAPES or Df != D or Hf < 1 or Wf < 1 or ((Hf + 1) // 2, (Wf + 1) // 2) != (Hc, Wc):
+        raise _lib.DmvsError(f"{what}: gy {tuple(gy.shape)} is not the output of a 5x5 stride-2 layer {WGRAD_K5S2_SHAPES} on "
+                             f"{tuple(fine_shape)} ([Ca,D,(Hf+1)//2,(Wf+1)//2] for [Ca/2,D,Hf,Wf])")
+    return Ca, D, Hf, Wf
+
+
+def conv2d_k5s2_wgrad_workspace(Ca: int, D: int, Hf: int, Wf: int, device) -> torch.Tensor:
+    """K3k's workspace, one per (shape class, device, stream): its size does not depend on the image."""
+    n = _lib.load().dmvs_conv2d_k5s2_wgrad_workspace(Ca, D, Hf, Wf)
+    if n <= 0:
+        raise _lib.DmvsError(f"conv2d_k5s2_wgrad: Ca = {Ca}, planes {D}, image {(Hf, Wf)} is not covered by the 5x5 stride-2 "
+                             "weight-gradient kernel")
+    return _workspace("k3k", n, device)
+
+
+def conv2d_k5s2_wgrad(x: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K3k.  x [Cb,D,Hf,Wf] (input of a 5x5 stride-2 pad-2 conv Cb -> Ca = 2 Cb on D independent planes), gy [Ca,D,Hc,Wc] (the gradient
+    on its output; Hc = (Hf + 1) // 2, Wc = (Wf + 1) // 2) -> the weight gradient [Ca,Cb,5,5],
+    dW[a,b,ky,kx] = sum gy[a,z,y,x] * x[b,z,2y+ky-2,2x+kx-2].  ``out``: buffer to write into; with ``accumulate`` the result is ADDED
+    to it (it must then be given).  ``workspace``: at least dmvs_conv2d_k5s2_wgrad_workspace floats (default: a cached buffer per device
+    and stream)."""
+    _req(x, gy, out, workspace)
+    Ca, D, Hf, Wf = _k5s2_dims("conv2d_k5s2_wgrad", gy, x.shape)
+    if accumulate and out is None:
+        raise _lib.DmvsError("conv2d_k5s2_wgrad: accumulate needs the buffer to add to (out)")
+    if out is None:
+        out = torch.empty((Ca, Ca // 2, 5, 5), dtype=torch.float32, device=x.device)
+    elif out.numel() != Ca * (Ca // 2) * 25:
+        raise _lib.DmvsError(f"conv2d_k5s2_wgrad: out {tuple(out.shape)} is not a [{Ca},{Ca // 2},5,5] weight")
+    if workspace is None:
+        workspace = conv2d_k5s2_wgrad_workspace(Ca, D, Hf, Wf, x.device)
+    elif workspace.numel() < _lib.load().dmvs_conv2d_k5s2_wgrad_workspace(Ca, D, Hf, Wf):
+        raise _lib.DmvsError("conv2d_k5s2_wgrad: workspace too small")
+    cost = None
+    if timer is not None:
+        nt = 25 * Ca * (Ca // 2)
+        cost = (2.0 * nt * D * gy.shape[2] * gy.shape[3], 4.0 * (gy.numel() + x.numel() + nt), None)
+    _launch(_lib.load().dmvs_conv2d_k5s2_wgrad, (_ptr(gy), _ptr(x), _ptr(out), _ptr(workspace), Ca, D, Hf, Wf, 1 if accumulate else 0),
+            f"wgrad_k5s2_{Ca}", "wgrad_k5s2", x, (gy, out, workspace), False, "conv2d_k5s2_wgrad", cost)
+    _log("conv2d_k5s2_wgrad")   # two dispatches per call: the partials and their sum
+    return out
+
+
+def conv2d_k5s2_dgrad(gy: torch.Tensor, w: torch.Tensor, fine_hw, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K3d.  gy [Ca,D,Hc,Wc] (the gradient on the output of a 5x5 stride-2 pad-2 conv Cb -> Ca = 2 Cb), w the layer's weight in
+    nn.Conv2d layout [Ca,Cb,5,5] as it lies, ``fine_hw`` = (Hf, Wf) of the layer's input (Hc = (Hf + 1) // 2: two fine extents give one
+    coarse one) -> the data gradient [Cb,D,Hf,Wf], every element written once.  ``out``: buffer to write into."""
+    _req(gy, w, out)
+    Hf, Wf = (int(n) for n in fine_hw)
+    Ca, D, Hf, Wf = _k5s2_dims("conv2d_k5s2_dgrad", gy, (int(gy.shape[0]) // 2, int(gy.shape[1]) if gy.dim() == 4 else 0, Hf, Wf))
+    Cb = Ca // 2
+    if w.numel() != Ca * Cb * 25 or w.dim() != 4 or tuple(w.shape[:2]) != (Ca, Cb):
+        raise _lib.DmvsError(f"conv2d_k5s2_dgrad: w {tuple(w.shape)} is not a [{Ca},{Cb},5,5] weight")
+    if out is None:
+        out = torch.empty((Cb, D, Hf, Wf), dtype=torch.float32, device=gy.device)
+    elif tuple(out.shape) != (Cb, D, Hf, Wf):
+        raise _lib.DmvsError(f"conv2d_k5s2_dgrad: out {tuple(out.shape)} is not the fine tensor {(Cb, D, Hf, Wf)}")
+    cost = None
+    if timer is not None:
+        nt = 25 * Ca * Cb
+        cost = (2.0 * nt * D * gy.shape[2] * gy.shape[3], 4.0 * (gy.numel() + out.numel() + nt), None)
+    _launch(_lib.load().dmvs_conv2d_k5s2_dgrad, (_ptr(gy), _ptr(w), _ptr(out), Ca, D, Hf, Wf),
+            f"dgrad_k5s2_{Ca}", "dgrad_k5s2", gy, (w, out), False, "conv2d_k5s2_dgrad", cost)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ K5 (training: BatchNorm + ReLU)
 BN_CHANNELS = (8, 16, 32, 64)   # the channel counts K5 takes (csrc/batchnorm.h)
 BN_CHUNK = 1024                 # elements of a chunk: 256 lanes x 4 floats; a share is a run of whole chunks

@@ -561,6 +561,30 @@ long dmvs_conv3d_wgrad_s2_workspace(int Ca, int Dc, int Hc, int Wc, int kdepth);
  * Negative DMVS_E* as dmvs_conv3d_wgrad_s2. */
 int dmvs_conv3d_wgrad_s2_plan(int Ca, int Dc, int Hc, int Wc, int kdepth);
 
+/* K3k / K3d: weight and data gradient of FeatureNet's 5x5 stride-2 pad-2 2D convolutions conv1.0 (8 -> 16) and conv2.0 (16 -> 32)
+ * (networks/module.py:289, :295) on the fp32 matrix cores (csrc/conv2d_k5s2_bwd.h, docs/kernels/K3k_conv_wgrad_k5s2.md) -- what
+ * autograd computes behind DMVS_CONV2D_K5S2.  A sample is D independent planes (K3's kdepth-1 layout); Cb = Ca / 2,
+ * Hc = (Hf + 1) / 2, Wc = (Wf + 1) / 2: even and odd fine extents.
+ *   gy         [Ca][D][Hc][Wc]: the gradient on the layer's output;  x [Cb][D][Hf][Wf]: its input;  w [Ca][Cb][5][5]: nn.Conv2d's weight
+ *   gw         [Ca][Cb][5][5] out: gw[a][b][ky][kx] (+)= sum_{z,y,x} gy[a][z][y][x] * x[b][z][2y+ky-2][2x+kx-2], zero outside `x`
+ *   gx         [Cb][D][Hf][Wf] out, every element written once:
+ *              gx[b][z][Y][X] = sum_{a,ky,kx : Y+2-ky = 2y, X+2-kx = 2x, 0 <= y < Hc, 0 <= x < Wc} gy[a][z][y][x] * w[a][b][ky][kx]
+ *   workspace  dmvs_conv2d_k5s2_wgrad_workspace(...) floats; partial sums, fully overwritten where read
+ *   accumulate 0: gw is overwritten; 1: the sum is added to gw (a batch runs as its samples one after the other)
+ * Ca in {16, 32}, else DMVS_EUNSUPPORTED; null pointers, extents < 1 (or above 2^21) or 2^22 tiles and more: DMVS_EINVAL.  The weight
+ * gradient is two launches (partials, then their sum in a fixed order), the data gradient one gather launch that reads `w` as it
+ * lies; no atomics: both are bitwise reproducible. */
+int dmvs_conv2d_k5s2_wgrad(const float* gy, const float* x, float* gw, float* workspace, int Ca, int D, int Hf, int Wf, int accumulate,
+                           dmvs_stream_t stream);
+int dmvs_conv2d_k5s2_dgrad(const float* gy, const float* w, float* gx, int Ca, int D, int Hf, int Wf, dmvs_stream_t stream);
+/* Workspace of dmvs_conv2d_k5s2_wgrad in floats: one partial [25][Ca][Ca / 2] per share, 256 shares at most -- it does not depend on
+ * the image.  0 for a shape the kernel is not compiled for or an extent < 1. */
+long dmvs_conv2d_k5s2_wgrad_workspace(int Ca, int D, int Hf, int Wf);
+/* Host only: the launch dmvs_conv2d_k5s2_wgrad will make, as tiles * 512 + workgroups.  tiles = D * ceil(Hc / 4) * ceil(Wc / 32) coarse
+ * tiles of 1 x 4 x 32; workgroups = the size of the first launch's grid (a multiple of 8, at most 256); workgroups past
+ * min(tiles, 256) exit at once and own no partial.  Negative DMVS_E* as dmvs_conv2d_k5s2_wgrad. */
+int dmvs_conv2d_k5s2_wgrad_plan(int Ca, int D, int Hf, int Wf);
+
 /* K2g: weight gradient of the 2-channel ends of the regularisation U-Nets, conv0 (2 -> 8) and `prob` (8 -> 2), 3x3x3, stride 1, pad 1
  * (csrc/conv3d_wgrad_c2.h, docs/kernels/K2g_conv_wgrad_c2.md) -- what autograd computes for the weight of the reference's conv0 block
  * and `prob` (networks/module.py:361, 379, 403, 421).  fp32 VALU, lane = voxel.

@@ -3,7 +3,8 @@
 DiffConv2d: K3 forward and data gradient, K3g weight gradient) against nn.Conv3d / nn.Conv2d on ATen (MIOpen) on the same MI355X, per
 sample (batch 1); and of the eight stride-2 / transposed layers between them (DiffConv3d / DiffConv2d at stride 2,
 DiffConvTranspose3d / DiffConvTranspose2d: K3 in both stride-2 modes, K3h weight gradient) against nn.Conv3d / nn.ConvTranspose3d and
-the 2D forms.  A strided row is named after its layer (conv1 / 3 / 5 going down, conv7 / 9 / 11 going up, the refine net's 2D conv5 /
+the 2D forms; and of FeatureNet's two 5x5 stride-2 layers conv1.0 / conv2.0 (DiffConv2d at kernel 5: K3 forward, K3d data gradient, K3k
+weight gradient; rows "*.feature.conv1.0" / "*.feature.conv2.0", D x H x W their coarse output) against nn.Conv2d.  A strided row is named after its layer (conv1 / 3 / 5 going down, conv7 / 9 / 11 going up, the refine net's 2D conv5 /
 conv7); its coarse volume is the volume of the square layer it sits next to (conv1 and conv11: conv2's, ...), its fine one twice that.
 
 Volumes per layer: the layer's volumes in the reference's training recipe (scripts/train.sh: 512 x 640, ndepths 48 / 32 / 8; rows
@@ -17,6 +18,7 @@ swapped every round.  Per row and arm:
   peak_mb   torch.cuda.max_memory_allocated over one forward + backward, minus what was allocated before it
 and the weight-gradient kernel alone (K3g, or K3h on the strided rows): its time and its fraction of the 157 TFLOP/s fp32 MFMA peak at
 2 * 9 * kd * Cout * Cin * (output voxels of the GEMM's reduction: D * H * W, coarse for K3h) FLOP.
+On the 5x5 rows also K3d alone and both kernels' fraction of the HBM floor (the bytes of their tensors at 8 TB/s).
 One JSON line; --md writes the table of profiles/conv_train.md.
 """
 import argparse
@@ -32,6 +34,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 
 PEAK_TF = 157.0
+HBM_TBS = 8.0
+
+# FeatureNet's 5x5 stride-2 layers: (row, Cb, fine (H, W)) -- conv1.0 reads the image-sized conv0 output, conv2.0 half of it
+ROWS_K5S2 = (("train.feature.conv1.0", 8, (512, 640)), ("train.feature.conv2.0", 16, (256, 320)),
+             ("c2.feature.conv1.0", 8, (1184, 1600)), ("c2.feature.conv2.0", 16, (592, 800)))
 
 # (row, C, kdepth, (D, H, W))
 ROWS = (
@@ -188,6 +195,42 @@ def main():
               f"{r['aten_peak_mb']:.0f} MB  K3h {r['k3g_ms']:.3f} ms = {r['k3g_tflops']:.1f} TF  gradients differ by {agree:.1e}",
               file=sys.stderr, flush=True)
         del x, gy, gh, ga, hip, aten, gw
+    for name, Cb, (Hf, Wf) in ROWS_K5S2:
+        if want and not any(s in name for s in want):
+            continue
+        Ca, Hc, Wc = 2 * Cb, (Hf + 1) // 2, (Wf + 1) // 2
+        g = torch.Generator(device="cpu").manual_seed(Ca + Hf)
+        x = torch.randn((1, Cb, Hf, Wf), generator=g).to(dev).requires_grad_(True)
+        gy = torch.randn((1, Ca, Hc, Wc), generator=g).to(dev)
+        hip = DiffConv2d(Cb, Ca, 5, stride=2, padding=2, bias=False).to(dev)
+        aten = nn.Conv2d(Cb, Ca, 5, stride=2, padding=2, bias=False).to(dev)
+        aten.load_state_dict(hip.state_dict())
+
+        def arm(m):
+            return lambda: torch.autograd.grad(m(x), [x, m.weight], gy)
+
+        gh, ga = arm(hip)(), arm(aten)()
+        agree = max(((a - b).abs().max() / b.abs().max()).item() for a, b in zip(gh, ga))
+        r = ab({"hip": arm(hip), "aten": arm(aten)}, args.reps, args.windows)
+        x4, gy4, w = x.detach().reshape(Cb, 1, Hf, Wf), gy.reshape(Ca, 1, Hc, Wc), hip.weight.detach()
+        gw, gx = torch.empty_like(w), torch.empty_like(x4)
+        k3k = lambda: ops.conv2d_k5s2_wgrad(x4, gy4, out=gw)             # noqa: E731
+        k3d = lambda: ops.conv2d_k5s2_dgrad(gy4, w, (Hf, Wf), out=gx)    # noqa: E731
+        k3k(), k3d()
+        flop, floor_ms = 2.0 * 25 * Ca * Cb * Hc * Wc, 4.0 * (x4.numel() + gy4.numel() + w.numel()) / (HBM_TBS * 1e12) * 1e3
+        r["k3g_ms"] = float(np.median([window(k3k, args.reps) for _ in range(args.windows)]))
+        r["k3d_ms"] = float(np.median([window(k3d, args.reps) for _ in range(args.windows)]))
+        r["k3g_tflops"], r["k3d_tflops"] = flop / (r["k3g_ms"] * 1e-3) / 1e12, flop / (r["k3d_ms"] * 1e-3) / 1e12
+        r["k3g_peak_fraction"], r["k3d_peak_fraction"] = r["k3g_tflops"] / PEAK_TF, r["k3d_tflops"] / PEAK_TF
+        r["k3g_hbm_fraction"], r["k3d_hbm_fraction"] = floor_ms / r["k3g_ms"], floor_ms / r["k3d_ms"]
+        r.update(C=f"{Cb}->{Ca}", kd=1, D=1, H=Hc, W=Wc, gradients_rel_diff=agree, kernel="K3k")
+        out["rows"][name] = r
+        print(f"# {name}: hip {r['hip_ms']['median']:.3f} [{r['hip_ms']['min']:.3f}, {r['hip_ms']['max']:.3f}] ms  aten "
+              f"{r['aten_ms']['median']:.3f} [{r['aten_ms']['min']:.3f}, {r['aten_ms']['max']:.3f}] ms  peak {r['hip_peak_mb']:.0f} / "
+              f"{r['aten_peak_mb']:.0f} MB  K3k {r['k3g_ms']:.3f} ms = {r['k3g_tflops']:.2f} TF, {r['k3g_hbm_fraction']:.2f} of the HBM floor  "
+              f"K3d {r['k3d_ms']:.3f} ms = {r['k3d_tflops']:.2f} TF, {r['k3d_hbm_fraction']:.2f} of the HBM floor  gradients differ by "
+              f"{agree:.1e}", file=sys.stderr, flush=True)
+        del x, gy, gh, ga, hip, aten, gw, gx
     print(json.dumps(out))
     if args.md:
         with open(args.md, "w") as f:
@@ -206,6 +249,17 @@ def markdown(out):
         lines.append(f"| {name} | {r['C']} | {r['kd']} | {r['D']} x {r['H']} x {r['W']} | {r['hip_ms']['median']:.3f} | "
                      f"{r['aten_ms']['median']:.3f} | {r['aten_over_hip']:.2f} | {r['hip_peak_mb']:.0f} | {r['aten_peak_mb']:.0f} | "
                      f"{r['k3g_ms']:.3f} | {r['k3g_tflops']:.1f} | {r['k3g_peak_fraction']:.2f} | {r['gradients_rel_diff']:.1e} |")
+    k5 = {n: r for n, r in out["rows"].items() if r.get("kernel") == "K3k"}
+    if k5:
+        lines += ["", "The 5x5 stride-2 rows: median [min, max] of both arms, and K3k / K3d alone (fraction of the 157 TFLOP/s fp32 MFMA peak; "
+                  f"HBM floor = the bytes of the kernel's tensors at {HBM_TBS:.0f} TB/s over its time).", "",
+                  "| layer | hip fwd+bwd | ATen fwd+bwd | K3k ms | K3k of 157 | K3k HBM floor / time | K3d ms | K3d of 157 | K3d HBM floor / time |",
+                  "|---|---|---|---|---|---|---|---|---|"]
+        for name, r in k5.items():
+            h, a = r["hip_ms"], r["aten_ms"]
+            lines.append(f"| {name} | {h['median']:.3f} [{h['min']:.3f}, {h['max']:.3f}] | {a['median']:.3f} [{a['min']:.3f}, {a['max']:.3f}] | "
+                         f"{r['k3g_ms']:.3f} | {r['k3g_peak_fraction']:.3f} | {r['k3g_hbm_fraction']:.2f} | {r['k3d_ms']:.3f} | "
+                         f"{r['k3d_peak_fraction']:.3f} | {r['k3d_hbm_fraction']:.2f} |")
     lines.append("")
     return "\n".join(lines)
 

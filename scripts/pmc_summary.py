@@ -21,6 +21,7 @@ DMVS_KERNELS = ("mfma_kernel", "wino_kernel", "warp_corr", "conv_cout2", "conv_d
                 "conv2d_c8_kernel", "conv0_fused_kernel", "coarse_kernel", "zmarch_kernel", "conv1_split_kernel", "depth_select_kernel",
                 "conv_wgrad_kernel", "conv_wgrad_reduce_kernel", "conv_wgrad_s2_kernel", "conv_wgrad_s2_reduce_kernel",
                 "conv_wgrad_c2_kernel", "conv_wgrad_c2_reduce_kernel",
+                "conv_wgrad_k5s2_kernel", "conv_wgrad_k5s2_reduce_kernel", "conv_dgrad_k5s2_kernel",
                 "bn_stats_kernel", "bn_apply_kernel", "bn_bwd_reduce_kernel", "bn_bwd_apply_kernel", "bn_bwd_fold_kernel")
 
 args = sys.argv[1:]
