@@ -260,7 +260,9 @@ def test_deconv_residual_prefetch_is_bit_identical(D, H, W):
 @pytest.mark.parametrize("case", WINO_CASES, ids=lambda c: "x".join(map(str, c)))
 def test_conv3d_wino(case):
     """K3w (Winograd F(2x2,3x3) on the fp32 MFMA) against ATen's direct fp32 convolution -- same tolerance as the
-    direct-form kernels' test -- and against K3 itself (re-association level)."""
+    direct-form kernels' test -- and against K3 itself (re-association level).
+    Parity: the 3D rows and conv0 are held to float64 with the criterion's own bound, on a walk of several tiles per workgroup, under
+    every `wino_stages` / `wino_persistent` / `zpad_skip` setting, in tests/test_winoconv_gpu.py (yardstick: tests/winoconv_ref.py)."""
     cin, cout, kd, D, H, W = case
     w = rnd(*((cout, cin) + ((3, 3, 3) if kd == 3 else (3, 3))), seed=cin * 100 + cout + kd, scale=1.0 / np.sqrt(cin * 9 * kd))
     layer, scale, shift = _layer(w, ops.CONV_S1, kd, bn=True, seed=cin + cout)
@@ -311,7 +313,9 @@ ZMARCH_CASES = [
 @pytest.mark.parametrize("case", ZMARCH_CASES, ids=lambda c: "x".join(map(str, c)))
 def test_conv3d_zmarch(case):
     """K3z (csrc/conv3d_zmarch.hip: conv2 in Winograd F(2x2,3x3) form, filters in registers, marching along z) against ATen's direct
-    fp32 convolution at the direct kernels' tolerance, against K3 itself, bit-identical run to run, every output written."""
+    fp32 convolution at the direct kernels' tolerance, against K3 itself, bit-identical run to run, every output written.
+    Parity: K3z is held to float64 with the criterion's own bound under every `k3z_zs` / `k3z_grid` cut of its columns in
+    tests/test_winoconv_gpu.py (yardstick: tests/winoconv_ref.py)."""
     D, H, W = case
     w = rnd(16, 16, 3, 3, 3, seed=161 + D, scale=1.0 / np.sqrt(16 * 27))
     layer, scale, shift = _layer(w, ops.CONV_S1, 3, bn=True, seed=32)
@@ -437,7 +441,9 @@ COARSE_CASES = [
 @pytest.mark.parametrize("case", COARSE_CASES, ids=lambda c: "x".join(map(str, c)))
 def test_conv3d_coarse(case):
     """K3r (csrc/conv3d_coarse.hip: conv4 / conv6 and their 2D forms, Winograd F(2x2,3x3) with register-stationary filters,
-    persistent workgroups) against ATen's direct fp32 convolution at the direct kernels' tolerance, and against K3 itself."""
+    persistent workgroups) against ATen's direct fp32 convolution at the direct kernels' tolerance, and against K3 itself.
+    Parity: K3r is held to float64 with the criterion's own bound on both loaders and store widths, at `k3r_grid` 256 and 32 and in
+    every dead-tap copy in tests/test_winoconv_gpu.py (yardstick: tests/winoconv_ref.py)."""
     cin, cout, kd, D, H, W = case
     w = rnd(*((cout, cin) + ((3, 3, 3) if kd == 3 else (3, 3))), seed=cin * 100 + cout + kd, scale=1.0 / np.sqrt(cin * 9 * kd))
     layer, scale, shift = _layer(w, ops.CONV_S1, kd, bn=True, seed=cin + cout)
