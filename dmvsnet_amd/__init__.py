@@ -22,6 +22,9 @@ from .bn import (DiffBatchNormReLU2d, DiffBatchNormReLU3d, DiffConvBlock2d, Diff
 from . import regnet  # noqa: F401  (the four regularisation networks on the differentiable layers; conv0 / prob: K2 + K2g)
 from .regnet import DiffCostRegNet, DiffCostRegNetPart, DiffCostRegNetPartRefine, DiffCostRegNetRefine  # noqa: F401
 
+from . import featurenet  # noqa: F401  (the differentiable FeatureNet: K3 + K3f for its rectangular layers, the whole network)
+from .featurenet import DiffFeatureConv2d, DiffFeatureConvBlock2d, DiffFeatureNet  # noqa: F401
+
 from . import eval_io  # noqa: F401  (PFM / cam I/O, eval dataset, Model.test step 1)
 from . import fusion   # noqa: F401  (geometric-consistency fusion filter, PLY)
 from . import cloud_eval  # noqa: F401  (DTU accuracy / completeness of a fused cloud)
@@ -35,4 +38,4 @@ __all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFea
            "diff_mvs_loss", "conv", "DiffConv3d", "DiffConv2d", "DiffConvTranspose3d",
            "DiffConvTranspose2d", "bn", "DiffBatchNormReLU3d", "DiffBatchNormReLU2d", "DiffConvBlock3d", "DiffDeconvBlock3d",
            "DiffConvBlock2d", "DiffDeconvBlock2d", "regnet", "DiffCostRegNetPart", "DiffCostRegNetPartRefine", "DiffCostRegNet",
-           "DiffCostRegNetRefine"]
+           "DiffCostRegNetRefine", "featurenet", "DiffFeatureConv2d", "DiffFeatureConvBlock2d", "DiffFeatureNet"]

@@ -98,6 +98,9 @@ SIGNATURES = {
     "dmvs_conv2d_k5s2_wgrad_workspace": (ctypes.c_long, [_i, _i, _i, _i]),
     "dmvs_conv2d_k5s2_wgrad_plan": (_i, [_i, _i, _i, _i]),
     "dmvs_conv2d_k5s2_dgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "dmvs_conv2d_wgrad_fpn": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "dmvs_conv2d_wgrad_fpn_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i, _i]),
+    "dmvs_conv2d_wgrad_fpn_plan": (_i, [_i, _i, _i, _i, _i, _i]),
     "dmvs_conv3d_wgrad_c2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dmvs_conv3d_wgrad_c2_workspace": (ctypes.c_long, [_i, _i, _i, _i, _i]),
     "dmvs_conv3d_wgrad_c2_plan": (_i, [_i, _i, _i, _i, _i]),

@@ -28,7 +28,9 @@ arguments and have their children (``.conv``, ``.bn``) and state-dict keys; each
 ``DiffBatchNormReLU*``.  ``bn=False`` or a layer shape the convolution classes refuse raises.  ``DiffConvBlock3d(2, 8, 3, padding=1)`` is
 conv0 as the reference builds it; ``prob`` has no BatchNorm and is a bare ``DiffConv3d(8, 2, ...)`` (``dmvsnet_amd.regnet`` builds the
 whole networks).  ``DiffConvBlock2d(8, 16, 5, stride=2, padding=2)`` and ``(16, 32, 5, stride=2, padding=2)`` are FeatureNet's conv1.0 /
-conv2.0 (networks/module.py:289, :295) on K3, K3d, K3k and K5.
+conv2.0 (networks/module.py:289, :295) on K3, K3d, K3k and K5.  The block around conv0.0 / conv0.1 is
+``dmvsnet_amd.featurenet.DiffFeatureConvBlock2d`` (``_DiffBlock`` on ``DiffFeatureConv2d``): with it no block of a training step is left on
+ATen.
 """
 from __future__ import annotations
 

@@ -11,8 +11,9 @@ third part) and FeatureNet's 5x5 stride-2 layers conv1.0 / conv2.0 (K3 forward, 
 
 Accepted at stride 1: kernel 3, padding 1, dilation 1, groups 1, no bias, in == out in {16, 32, 64} -- conv2 / conv4 / conv6 of
 CostRegNet_part, conv2 / conv4 and the 2D conv6 of CostRegNet_part_refine, conv1.1 / 1.2 / 2.1 / 2.2 and out2 of FeatureNet.  Everything
-else raises in the constructor: there is no ATen fallback.  FeatureNet's 1x1 layers, conv0.0 / conv0.1 and out3 stay on ATen
-(``dmvsnet_amd.MVSNet.train()`` still raises); BatchNorm + ReLU run on K5 (``dmvsnet_amd.bn``: ``DiffBatchNormReLU3d`` / ``2d``, and the
+else raises in the constructor: there is no ATen fallback.  FeatureNet's 1x1 layers, conv0.0 / conv0.1 and out3 are refused here and
+run on ``dmvsnet_amd.featurenet.DiffFeatureConv2d`` (K3 + K3f): no layer is left on ATen (``dmvsnet_amd.MVSNet.train()`` still raises:
+the parts exist, their assembly does not); BatchNorm + ReLU run on K5 (``dmvsnet_amd.bn``: ``DiffBatchNormReLU3d`` / ``2d``, and the
 blocks ``DiffConvBlock3d`` ... that pair these layers with it); ``dmvsnet_amd.regnet`` builds the four regularisation networks.
 
 * forward: ``ops.conv3d(x[b], layer, backend="mfma")`` per sample, bit for bit, the layer being the bare convolution (no scale / shift /

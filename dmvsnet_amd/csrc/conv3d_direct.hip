@@ -544,3 +544,6 @@ extern "C" int dmvs_conv3d_direct(const float* in, float* out, const float* w_pa
 
 // K3k / K3d: weight and data gradient of FeatureNet's 5x5 stride-2 layers (device code, launchers and its four C entries)
 #include "conv2d_k5s2_bwd.h"
+
+// K3f: weight and bias gradient of FeatureNet's rectangular stride-1 layers (device code, launcher and its three C entries)
+#include "conv2d_wgrad_fpn.h"

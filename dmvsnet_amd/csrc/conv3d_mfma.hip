@@ -838,6 +838,11 @@ const Cfg kCfgs[] = {
     {32, 64, DMVS_CONV2D_K1, 1, 32, 2, CI_K1},  // out1
     {16, 32, DMVS_CONV2D_K1, 1, 32, 1, CI_K1},  // inner1
     {8, 32, DMVS_CONV2D_K1, 1, 32, 1, CI_K1},   // inner2
+    // training only: the data gradients of out3, out1, inner1, inner2 (the layer out -> in on the transposed, tap-flipped weight)
+    {16, 32, DMVS_CONV_S1, 1, 32, 1, 4},        // d out3
+    {64, 32, DMVS_CONV2D_K1, 1, 32, 1, CI_K1},  // d out1
+    {32, 16, DMVS_CONV2D_K1, 1, 16, 1, CI_K1},  // d inner1
+    {32, 8, DMVS_CONV2D_K1, 1, 16, 1, CI_K1},   // d inner2 (Cout 8 on the 16-row MFMA, as conv0.0 / conv0.1)
 };
 
 int taps_of(int mode, int kdepth) {
@@ -1077,12 +1082,15 @@ extern "C" int dmvs_conv3d_mfma(const float* in, float* out, const float* w_pack
             if (Cin == 16 && Cout == 16) return launch_conv<16, 1, 1, 1, CI_F1>(a, st);
             if (Cin == 32 && Cout == 32) return launch_conv<32, 1, 1, 1, CI_F2>(a, st);
             if (Cin == 32 && Cout == 16) return launch_conv<16, 1, 1, 1, CI_FO3>(a, st);
+            if (Cin == 16 && Cout == 32) return launch_conv<32, 1, 1, 1, 4>(a, st);
         }
     } else if (mode == DMVS_CONV2D_K1 && !k3) {
         a.Do = D; a.Ho = H; a.Wo = W;
         if (Cin == 32 && Cout == 64) return launch_conv<32, 2, 1, 1, CI_K1, 1>(a, st);
         if (Cin == 16 && Cout == 32) return launch_conv<32, 1, 1, 1, CI_K1, 1>(a, st);
         if (Cin == 8 && Cout == 32) return launch_conv<32, 1, 1, 1, CI_K1, 1>(a, st);
+        if (Cin == 64 && Cout == 32) return launch_conv<32, 1, 1, 1, CI_K1, 1>(a, st);
+        if (Cin == 32 && (Cout == 16 || Cout == 8)) return launch_conv<16, 1, 1, 1, CI_K1, 1>(a, st);
     } else if (mode == DMVS_CONV2D_K5S2 && !k3) {
         a.Do = D; a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2;
         if (Cin == 8 && Cout == 16) return launch_conv<16, 1, 2, 1, CI_K5A, 5>(a, st);

@@ -408,7 +408,8 @@ class MVSNet(nn.Module):
     # -- lifecycle ---------------------------------------------------------------------------------
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError("dmvsnet_amd.MVSNet is the inference hot path; training is out of scope")
+            raise NotImplementedError("dmvsnet_amd.MVSNet is the inference hot path; the differentiable parts exist (DiffFeatureNet, DiffCostAgg, "
+                                      "DiffCostRegNet, DiffDepthNet), their assembly into a training model does not")
         return super().train(False)
 
     def _invalidate(self):

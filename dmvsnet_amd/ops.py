@@ -1207,6 +1207,97 @@ def conv2d_k5s2_dgrad(gy: torch.Tensor, w: torch.Tensor, fine_hw, out: Optional[
     return out
 
 
+# ------------------------------------------------------------------------------------------ K3f (training: FeatureNet's rectangular stride-1 convs)
+WGRAD_FPN_TILE = (1, 4, 32)   # tile (plane, y, x) of K3f: dmvs_conv2d_wgrad_fpn_plan counts these (csrc/conv2d_wgrad_fpn.h)
+# (Cin, Cout, kernel): conv0.0, conv0.1, out3, out1, inner1, inner2 (networks/module.py:284, :285, :309, :301, :305, :306)
+FPN_SHAPES = ((3, 8, 3), (8, 8, 3), (32, 16, 3), (32, 64, 1), (16, 32, 1), (8, 32, 1))
+FPN_BIAS_SHAPES = ((16, 32, 1), (8, 32, 1))   # ... of which these two have a bias
+
+
+def pack_index_mfma_fpn(cin: int, cout: int, ksize: int, transposed_flipped: bool, device=None) -> torch.Tensor:
+    """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K3's weight packing for the layer
+    ``(cin, cout, ksize)`` of FPN_SHAPES, weight ``w`` [cout,cin,ksize,ksize]: ``torch.cat((w.reshape(-1), zeros(1)))[index]`` equals,
+    bit for bit, ``pack_mfma(w, cin, cout, mode, 1)`` with mode CONV_S1 (kernel 3) or CONV2D_K1 (kernel 1) -- for cin = 3 the packing of
+    ``w`` with a zero fourth channel, as make_layer packs conv0.0.  ``transposed_flipped``: the index of
+    ``pack_mfma(w.transpose(0, 1).flip(2, 3), cout, cin, mode, 1)`` instead -- the weight of the layer's data gradient, a layer
+    cout -> cin (conv0.0 has none: the image takes no gradient).  These packings are selections with zeros (the zero channel, the zero
+    rows of 8 output channels on the 16-row MFMA): a zero selects the one appended slot, index n = cin * cout * ksize^2.  Derived once
+    on the host by packing ``iota + 1`` through the library's packer; every weight element must be selected exactly once."""
+    def build():
+        if (cin, cout, ksize) not in FPN_SHAPES or (transposed_flipped and cin == 3):
+            raise _lib.DmvsError(f"pack_index_mfma_fpn: ({cin}, {cout}, {ksize}), transposed_flipped = {transposed_flipped} is no layer "
+                                 f"of FeatureNet's head {FPN_SHAPES} (conv0.0 has no data gradient)")
+        n = cin * cout * ksize * ksize
+        iota = (torch.arange(n, dtype=torch.float32) + 1.0).reshape(cout, cin, ksize, ksize)   # (n + 1 < 2^24: the iota travels as fp32)
+        lin, lout = cin, cout
+        if transposed_flipped:
+            iota, lin, lout = iota.transpose(0, 1).flip(2, 3).contiguous(), cout, cin
+        if lin == 3:
+            iota, lin = torch.cat((iota, torch.zeros_like(iota[:, :1])), 1).contiguous(), 4
+        packed = pack_mfma(iota, lin, lout, CONV_S1 if ksize == 3 else CONV2D_K1, 1)
+        if packed is None:
+            raise _lib.DmvsError(f"pack_index_mfma_fpn: K3 does not compile the layer {lin} -> {lout}, kernel {ksize}")
+        idx = packed.to(torch.int64) - 1
+        idx[idx < 0] = n
+        if not torch.equal(torch.bincount(idx, minlength=n + 1)[:n], torch.ones(n, dtype=torch.int64)):
+            raise _lib.DmvsError(f"pack_index_mfma_fpn: the packing of {lin} -> {lout}, kernel {ksize} does not select every weight "
+                                 "element exactly once")
+        return idx
+    return _pack_index(("fpn", int(cin), int(cout), int(ksize), bool(transposed_flipped)), build, device)
+
+
+def _wgrad_fpn_dims(x: torch.Tensor, gy: torch.Tensor, ksize: int):
+    if x.dim() != 4 or gy.dim() != 4 or x.shape[1:] != gy.shape[1:] or (int(x.shape[0]), int(gy.shape[0]), int(ksize)) not in FPN_SHAPES:
+        raise _lib.DmvsError(f"conv2d_wgrad_fpn: x {tuple(x.shape)} and gy {tuple(gy.shape)} must be [Cin,D,H,W] and [Cout,D,H,W] of the "
+                             f"same planes with (Cin, Cout, kernel = {ksize}) in {FPN_SHAPES}")
+    return (int(x.shape[0]), int(gy.shape[0]), *(int(n) for n in x.shape[1:]))
+
+
+def conv2d_wgrad_fpn_workspace(Cin: int, Cout: int, ksize: int, D: int, H: int, W: int, device) -> torch.Tensor:
+    """K3f's workspace, one per (shape class, device, stream): its size does not depend on D, H, W."""
+    n = _lib.load().dmvs_conv2d_wgrad_fpn_workspace(Cin, Cout, ksize, D, H, W)
+    if n <= 0:
+        raise _lib.DmvsError(f"conv2d_wgrad_fpn: (Cin, Cout, kernel) = {(Cin, Cout, ksize)}, planes {(D, H, W)} is not covered by the "
+                             "weight-gradient kernel")
+    return _workspace("k3f", n, device)
+
+
+def conv2d_wgrad_fpn(x: torch.Tensor, gy: torch.Tensor, ksize: int, out: Optional[torch.Tensor] = None,
+                     bias_out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                     workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K3f.  x [Cin,D,H,W], gy [Cout,D,H,W] (input of a stride-1 conv of kernel ``ksize``, padding ``ksize // 2``, on D independent
+    planes and the gradient on its output), (Cin, Cout, ksize) in FPN_SHAPES -> the weight gradient [Cout,Cin,ksize,ksize].
+    ``bias_out`` ([Cout], the two layers of FPN_BIAS_SHAPES only): also the bias gradient, written there by the same launch.
+    ``out``: buffer to write into; with ``accumulate`` both results are ADDED to their buffers (``out`` must then be given).
+    ``workspace``: at least dmvs_conv2d_wgrad_fpn_workspace floats (default: a cached buffer per device and stream)."""
+    _req(x, gy, out, bias_out, workspace)
+    Cin, Cout, D, H, W = _wgrad_fpn_dims(x, gy, ksize)
+    if accumulate and out is None:
+        raise _lib.DmvsError("conv2d_wgrad_fpn: accumulate needs the buffer to add to (out)")
+    if bias_out is not None:
+        if (Cin, Cout, ksize) not in FPN_BIAS_SHAPES:
+            raise _lib.DmvsError(f"conv2d_wgrad_fpn: the layer {(Cin, Cout, ksize)} has no bias (only {FPN_BIAS_SHAPES} have)")
+        if bias_out.numel() != Cout:
+            raise _lib.DmvsError(f"conv2d_wgrad_fpn: bias_out {tuple(bias_out.shape)} is not a [{Cout}] bias")
+    if out is None:
+        out = torch.empty((Cout, Cin, ksize, ksize), dtype=torch.float32, device=x.device)
+    elif out.numel() != Cout * Cin * ksize * ksize:
+        raise _lib.DmvsError(f"conv2d_wgrad_fpn: out {tuple(out.shape)} is not a [{Cout},{Cin},{ksize},{ksize}] weight")
+    if workspace is None:
+        workspace = conv2d_wgrad_fpn_workspace(Cin, Cout, ksize, D, H, W, x.device)
+    elif workspace.numel() < _lib.load().dmvs_conv2d_wgrad_fpn_workspace(Cin, Cout, ksize, D, H, W):
+        raise _lib.DmvsError("conv2d_wgrad_fpn: workspace too small")
+    cost = None
+    if timer is not None:
+        nt = ksize * ksize * Cin * Cout
+        cost = (2.0 * nt * D * H * W, 4.0 * ((Cin + Cout) * D * H * W + nt), None)
+    _launch(_lib.load().dmvs_conv2d_wgrad_fpn,
+            (_ptr(x), _ptr(gy), _ptr(out), _ptr(bias_out), _ptr(workspace), Cin, Cout, D, H, W, ksize, 1 if accumulate else 0),
+            f"wgrad_fpn_{Cin}to{Cout}k{ksize}", "wgrad_fpn", x, (gy, out, bias_out, workspace), False, "conv2d_wgrad_fpn", cost)
+    _log("conv2d_wgrad_fpn")   # two dispatches per call: the partials and their sum
+    return out
+
+
 # ------------------------------------------------------------------------------------------ K5 (training: BatchNorm + ReLU)
 BN_CHANNELS = (8, 16, 32, 64)   # the channel counts K5 takes (csrc/batchnorm.h)
 BN_CHUNK = 1024                 # elements of a chunk: 256 lanes x 4 floats; a share is a run of whole chunks

@@ -18,7 +18,8 @@ constructor (no ATen fallback).
   K2g for the weight gradient.
 
 The three skip additions of a part, the channel ``cat`` of the pair and the refine part's ``squeeze(2)`` / ``unsqueeze(2)`` around its
-2D levels stay torch ops: they are elementwise (or views) and at the memory roofline already.
+2D levels stay torch ops: they are elementwise (or views) and at the memory roofline already.  ``dmvsnet_amd.featurenet`` does the same
+for FeatureNet; between them no ATen convolution or normalisation is left in a training step.
 
 Extents: the full part halves D, H, W three times and adds the up-sampled levels back, so all three must be multiples of 8.  The refine
 part halves D twice down to ONE plane (its conv5 .. conv7 are 2D layers on [B,C,H,W]), so D must be 4, and H, W multiples of 8.

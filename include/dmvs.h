@@ -585,6 +585,33 @@ long dmvs_conv2d_k5s2_wgrad_workspace(int Ca, int D, int Hf, int Wf);
  * min(tiles, 256) exit at once and own no partial.  Negative DMVS_E* as dmvs_conv2d_k5s2_wgrad. */
 int dmvs_conv2d_k5s2_wgrad_plan(int Ca, int D, int Hf, int Wf);
 
+/* K3f: weight and bias gradient of FeatureNet's rectangular stride-1 2D convolutions on the fp32 matrix cores
+ * (csrc/conv2d_wgrad_fpn.h, docs/kernels/K3f_conv_wgrad_fpn.md) -- what autograd computes for the weight of conv0.0 (3 -> 8, 3x3;
+ * networks/module.py:284), conv0.1 (8 -> 8, 3x3; :285), out1 (32 -> 64, 1x1; :301), inner1 (16 -> 32, 1x1, bias; :305), inner2
+ * (8 -> 32, 1x1, bias; :306) and out3 (32 -> 16, 3x3; :309), and for the bias of the two that have one.  A sample is D independent
+ * planes (K3's kdepth-1 layout); ksize 3 means padding 1, ksize 1 padding 0; stride 1.
+ * (Their forward is dmvs_conv3d_mfma in DMVS_CONV_S1 / DMVS_CONV2D_K1; their data gradient is the same entry on the layer Cout -> Cin
+ * with the weight transposed in (co, ci) and flipped in every tap.)
+ *   x          [Cin][D][H][W]: the layer's input;  gy [Cout][D][H][W]: the gradient on its output
+ *   gw         [Cout][Cin][ksize][ksize] out (nn.Conv2d layout):
+ *              gw[co][ci][ky][kx] (+)= sum_{d,y,x} gy[co][d][y][x] * x[ci][d][y+ky-ksize/2][x+kx-ksize/2], zero outside the plane
+ *   gbias      [Cout] out or NULL: gbias[co] (+)= sum_{d,y,x} gy[co][d][y][x], from the same launch (one more GEMM column whose x value
+ *              is the constant 1).  Only inner1 and inner2 take one; non-NULL for another layer: DMVS_EINVAL
+ *   workspace  dmvs_conv2d_wgrad_fpn_workspace(...) floats; partial sums, fully overwritten where read
+ *   accumulate 0: gw and gbias are overwritten; 1: the sums are added to them (a batch runs as its samples one after the other)
+ * (Cin, Cout, ksize) in {(3,8,3), (8,8,3), (32,16,3), (32,64,1), (16,32,1), (8,32,1)}, else DMVS_EUNSUPPORTED; null pointers, extents
+ * < 1 or 2^22 tiles and more: DMVS_EINVAL.  Any H, W >= 1.  Two launches (partials, then their sum in a fixed order); no atomics:
+ * bitwise reproducible. */
+int dmvs_conv2d_wgrad_fpn(const float* x, const float* gy, float* gw, float* gbias, float* workspace, int Cin, int Cout, int D, int H,
+                          int W, int ksize, int accumulate, dmvs_stream_t stream);
+/* Workspace of dmvs_conv2d_wgrad_fpn in floats: one partial [Cout][Cin * ksize * ksize (+ 1 for the bias column)] per share, 256 shares
+ * at most -- it does not depend on D, H, W.  0 for a shape the kernel is not compiled for or an extent < 1. */
+long dmvs_conv2d_wgrad_fpn_workspace(int Cin, int Cout, int ksize, int D, int H, int W);
+/* Host only: the launch dmvs_conv2d_wgrad_fpn will make, as tiles * 512 + workgroups.  tiles = D * ceil(H / 4) * ceil(W / 32) tiles of
+ * 1 x 4 x 32; workgroups = the size of the first launch's grid (a multiple of 8, at most 256); workgroups past min(tiles, 256) exit at
+ * once and own no partial.  Negative DMVS_E* as dmvs_conv2d_wgrad_fpn. */
+int dmvs_conv2d_wgrad_fpn_plan(int Cin, int Cout, int ksize, int D, int H, int W);
+
 /* K2g: weight gradient of the 2-channel ends of the regularisation U-Nets, conv0 (2 -> 8) and `prob` (8 -> 2), 3x3x3, stride 1, pad 1
  * (csrc/conv3d_wgrad_c2.h, docs/kernels/K2g_conv_wgrad_c2.md) -- what autograd computes for the weight of the reference's conv0 block
  * and `prob` (networks/module.py:361, 379, 403, 421).  fp32 VALU, lane = voxel.
