@@ -21,33 +21,11 @@ import torch
 from dmvsnet_amd import MVSNet, eval_io, synth
 from dmvsnet_amd._lib import DmvsError
 from dmvsnet_amd.fusion import ScanFusion, ViewFilter, fuse_scene, fuse_view, read_camera_parameters
+from fusion_ref import _check_xyz, _ulps  # noqa: F401  (the 1-ulp rule, shared with test_fusion_ref_gpu.py)
 from test_fusion import CONF, PAIRS, _plane_depths, _scene
 from test_scan_cpu import dtu_like_pairs, write_scene
 
 pytestmark = pytest.mark.gpu
-
-
-def _ulps(a, b):
-    """Per-element distance in fp32 ulps (a, b: float32 arrays of one shape)."""
-    ia = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
-    ib = np.asarray(b, np.float32).view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7fffffff), ia)
-    ib = np.where(ib < 0, -(ib & 0x7fffffff), ib)
-    return np.abs(ia - ib)
-
-
-def _check_xyz(a, b):
-    """[N,3] fp32 point sets in the same order: every coordinate within 1 ulp, or -- where the fp64 sum cancels to
-    (almost) zero and its sign or exponent depends on the reduction order (torch.mm in ViewFilter.finish vs the emit
-    kernel's fma chain) -- within fp64 rounding of the point's scale.  -> number of differing values."""
-    a, b = np.asarray(a, np.float32).reshape(-1, 3), np.asarray(b, np.float32).reshape(-1, 3)
-    assert a.shape == b.shape
-    if not a.size:
-        return 0
-    scale = np.maximum(np.abs(a).max(1, keepdims=True), 1.0).astype(np.float64)
-    ok = (_ulps(a, b) <= 1) | (np.abs(a.astype(np.float64) - b) <= 1e-12 * scale)
-    assert ok.all(), (int((~ok).sum()), a[~ok.any(1)][:3], b[~ok.any(1)][:3])
-    return int((a.view(np.int32) != b.view(np.int32)).sum())
 
 
 def _dev(a):
