@@ -29,7 +29,7 @@ from oracle import dmvs_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 8.0
+FACTOR = 8.0   # K1b per case table, guarded, with one-hot probes and 16 views: tests/test_warp_corr_grad_gpu.py
 
 
 @pytest.fixture(autouse=True)
