@@ -18,10 +18,7 @@
 //            read at a per-lane offset.  Loads are checked against Hf, Wf; outside the tensor zeros are staged: no global address is
 //            formed outside the two tensors, on ragged tiles and on the missing last row / column of an odd extent alike.
 //   banks    K3h's rule: the paired taps differ by an offset that is 2 mod 4 (MF 16) resp. odd (MF 32); derivation in the doc.
-//   grid     persistent, S = min(tiles, 256) shares, share s walks [s tiles / S, (s + 1) tiles / S) (x fastest, then y, then the plane),
-//            workgroups in xcd_grid order.
-//   sums     three levels in a fixed order, as K3g / K3h: tile = one MFMA chain from zero, tiles added to the share's running sum,
-//            partials [S][tap][a][b] added by the reduce kernel in the order s = 0 .. S - 1.  Bitwise reproducible.
+//   grid, sums   wgrad_share.h, one block; the tile's MFMA chain and the store of the partial [S][tap][a][b] are K3h's own functions.
 //
 // K3d is a gather: every fine pixel is written exactly once, by the lane that owns (b, z, j, i, py, px).
 //   MFMA     v_mfma_f32_16x16x4_f32 for both shapes: M = 16 fine-channel rows, N = 16 coarse pixels of a row, K = 4 coarse channels of
@@ -32,14 +29,16 @@
 //   tile     8 rows x 32 columns of (j, i) = 16 x 64 fine pixels, the coarse tile with a one-pixel halo in LDS (zeros outside the
 //            coarse grid), channel stride 16 mod 32.  A wave owns 2 rows x 2 column blocks of 16 and all four parity classes: a dY
 //            fragment is read once per tap and k-step and feeds every class that has the tap.
-//   grid     persistent: min(tiles, 256) workgroups, contiguous tile ranges in xcd_grid order, so the weights are staged once.
+//   grid     the shares' walk (wgrad_share.h) without their sums: every workgroup stages the weights once.
 #pragma once
-#include "conv3d_wgrad.h"
+#include "conv3d_wgrad_s2.h"
+#include "wgrad_share.h"
 
 namespace k5s2 {
 
 using wgrad::Frag;
-using wgrad::kMaxWg;
+using wgrad_s2::store_partial;
+using wgrad_s2::tile_chain;
 
 constexpr int kTX = 32;
 constexpr int kTY = 4;   // coarse rows of a K3k tile; dmvs_conv2d_k5s2_wgrad_plan counts kTY x kTX tiles
@@ -82,8 +81,7 @@ struct Args {
     const float* x;     // fine   [Cb][D][Hf][Wf]
     float* ws;
     int Ca, D, Hf, Wf, Hc, Wc;
-    int nx, ny, ntiles;   // tile grid: nx * ny * D tiles
-    int S;                // shares = workgroups with work
+    wshare::Grid g;   // one block
 };
 
 template <int MF>
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_k5s2_kernel(Args a) {
     typedef Frag<MF> F;
     typedef typename F::acc_t acc_t;
     typedef Geom<MF> G;
-    constexpr int CB = G::CB, SPW = G::SPW, IY = G::IY, OB = G::OB, RS = G::RS, FS = G::FS, AS = G::AS, KK = G::KK, TX = kTX, TY = kTY;
+    constexpr int CB = G::CB, SPW = G::SPW, IY = G::IY, OB = G::OB, RS = G::RS, FS = G::FS, AS = G::AS, TX = kTX, TY = kTY;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* fs = smem;
     float* as = smem + CB * FS;
@@ -100,10 +98,9 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_k5s2_kernel(Args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ln = lane % MF, lk = lane / MF;
     const int lq = ln / CB, lb = ln % CB;   // this lane's half of the slot and its fine channel
-    const int per = (a.S + 7) >> 3;
-    const int s = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (s >= a.S) return;
-    const int t0 = (int)((long)s * a.ntiles / a.S), t1 = (int)((long)(s + 1) * a.ntiles / a.S);
+    const int s = wshare::place(a.g, blockIdx.x);
+    if (s < 0) return;
+    const int t0 = wshare::first_tile(a.g, s), t1 = wshare::first_tile(a.g, s + 1);
     const size_t cplane = (size_t)a.Hc * a.Wc, cvol = cplane * a.D;
     const size_t fplane = (size_t)a.Hf * a.Wf, fvol = fplane * a.D;
 
@@ -128,15 +125,10 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_k5s2_kernel(Args a) {
         for (int r = 0; r < F::ACC; ++r) run[j][r] = 0.f;
 
     for (int tile = t0; tile < t1; ++tile) {
-        const int bx = tile % a.nx, rr = tile / a.nx, by = rr % a.ny, z = rr / a.ny;
-        const int x0 = bx * TX, y0 = by * TY;
+        const wshare::Tile t = wshare::decode(a.g, tile);
+        const int x0 = t.bx * TX, y0 = t.by * TY, z = t.z;
         __syncthreads();   // every wave is done reading the previous tile
-        for (int i = tid; i < MF * TY * TX; i += 256) {
-            const int c = i / (TY * TX), r = i % (TY * TX), y = y0 + r / TX, x = x0 + r % TX;
-            float v = 0.f;
-            if (y < a.Hc && x < a.Wc) v = a.gy[(size_t)c * cvol + z * cplane + (size_t)y * a.Wc + x];
-            as[c * AS + r] = v;
-        }
+        wshare::stage_rows<MF, TY, TX>(as, AS, a.gy, 0, MF, cvol, cplane, z, y0, x0, a.Hc, a.Wc, tid);
         // the fine halo: columns 2 x0 - 2 .. 2 x0 + 2 TX of rows 2 y0 - 2 .. 2 y0 + 2 TY, read along x and written split by parity:
         // column 2 x0 - 2 + f -> [f / 2] (f even), [OB + f / 2] (f odd)
         constexpr int FW = 2 * TX + 3;
@@ -149,68 +141,30 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_k5s2_kernel(Args a) {
             fs[c * FS + py * RS + ((f & 1) ? OB + (f >> 1) : (f >> 1))] = v;
         }
         __syncthreads();
-        acc_t acc[SPW];
-#pragma unroll
-        for (int j = 0; j < SPW; ++j)
-#pragma unroll
-            for (int r = 0; r < F::ACC; ++r) acc[j][r] = 0.f;
-        const float* pa = as + ln * AS + lk;
-#pragma unroll 1
-        for (int y = 0; y < TY; ++y) {
-#pragma unroll
-            for (int g = 0; g < TX / KK; ++g) {
-                const float av = pa[y * TX + g * KK];
-#pragma unroll
-                for (int j = 0; j < SPW; ++j) acc[j] = F::mfma(av, pb[j][2 * y * RS + g * KK], acc[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < SPW; ++j) run[j] += acc[j];
+        tile_chain<MF, SPW, TY, RS>(as + ln * AS + lk, pb, run);
     }
-
-    // partial of this share: ws[s][tap][a][b]; the CB lanes of a tap's row write CB contiguous floats
-    float* w = a.ws + (size_t)s * kNT * a.Ca * CB;
-#pragma unroll
-    for (int j = 0; j < SPW; ++j) {
-        if (tap[j] >= 0) {
-#pragma unroll
-            for (int r = 0; r < F::ACC; ++r) w[((size_t)tap[j] * a.Ca + F::row(r, lk)) * CB + lb] = run[j][r];
-        }
-    }
+    store_partial<MF, CB, SPW>(a.ws + (size_t)s * kNT * a.Ca * CB, a.Ca, 0, lk, lb, tap, run);
 }
 
 // gw[a][b][tap] (+)= sum_{s = 0 .. S-1} ws[s][tap][a][b], s ascending.  One thread per element, in workspace order.
 __global__ __launch_bounds__(256) void conv_wgrad_k5s2_reduce_kernel(const float* __restrict__ ws, float* __restrict__ gw, int Ca, int Cb,
                                                                       int S, int accumulate) {
-    const int n = kNT * Ca * Cb, e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    float sum = ws[e];
-    for (int s = 1; s < S; ++s) sum += ws[(size_t)s * n + e];
-    const int t = e / (Ca * Cb), ca = (e / Cb) % Ca, cb = e % Cb;
-    float* o = gw + ((size_t)ca * Cb + cb) * kNT + t;
-    *o = accumulate ? *o + sum : sum;
+    wshare::reduce(ws, kNT * Ca * Cb, S, accumulate, [=](int e) { return wshare::tap_last(gw, e, Ca, Cb, kNT); });
 }
 
 inline bool shape_ok(int Ca) { return Ca == 16 || Ca == 32; }
 
-// the coarse extents and the tile grid of ty x tx coarse pixels; false: an extent < 1 or too large, or >= 2^22 tiles
-inline bool tile_grid(int D, int Hf, int Wf, int ty, int tx, int& Hc, int& Wc, int& nx, int& ny, int& ntiles) {
-    if (D < 1 || Hf < 1 || Wf < 1) return false;
+// the coarse extents and the one-block grid of ty x tx coarse pixels; false: an extent < 1 or too large, or >= 2^22 tiles
+inline bool tile_grid(int D, int Hf, int Wf, int ty, int tx, int& Hc, int& Wc, wshare::Grid& g) {
     if (Hf > (1 << 21) || Wf > (1 << 21) || D > (1 << 21)) return false;   // 2 * coarse extent + 2 stays an int
     Hc = (Hf + 1) / 2; Wc = (Wf + 1) / 2;
-    nx = ceil_div(Wc, tx); ny = ceil_div(Hc, ty);
-    const long nt = (long)nx * ny * D;
-    if (nt >= (1L << 22)) return false;   // the plan packs the tile count into 22 bits (indices are 64-bit throughout)
-    ntiles = (int)nt;
-    return true;
+    return wshare::grid(D, Hc, Wc, ty, tx, 1, g);
 }
 
 // the launch geometry of K3k, one source of truth for the launcher, the workspace size and the plan
 inline bool geometry(int Ca, int D, int Hf, int Wf, Args& a) {
-    if (!tile_grid(D, Hf, Wf, kTY, kTX, a.Hc, a.Wc, a.nx, a.ny, a.ntiles)) return false;
     a.Ca = Ca; a.D = D; a.Hf = Hf; a.Wf = Wf;
-    a.S = a.ntiles < kMaxWg ? a.ntiles : kMaxWg;
-    return true;
+    return tile_grid(D, Hf, Wf, kTY, kTX, a.Hc, a.Wc, a.g);
 }
 
 template <int MF>
@@ -218,13 +172,8 @@ int launch(const Args& a, float* gw, int accumulate, hipStream_t st) {
     typedef Geom<MF> G;
     constexpr size_t lds = (size_t)G::LDS_F * sizeof(float);
     static_assert(lds <= 160 * 1024, "the two tiles must fit the 160 KB LDS");
-    auto kernel = conv_wgrad_k5s2_kernel<MF>;
-    if (int e = dmvs_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
-    kernel<<<dim3(xcd_grid(a.S)), 256, lds, st>>>(a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-    const int n = kNT * a.Ca * G::CB;
-    conv_wgrad_k5s2_reduce_kernel<<<dim3(ceil_div(n, 256)), 256, 0, st>>>(a.ws, gw, a.Ca, G::CB, a.S, accumulate);
-    DMVS_LAUNCH_CHECK();
+    return wshare::launch(conv_wgrad_k5s2_kernel<MF>, a, lds, st, conv_wgrad_k5s2_reduce_kernel, kNT * a.Ca * G::CB, a.ws, gw, a.Ca, G::CB,
+                          a.g.S, accumulate);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ K3d
@@ -245,8 +194,7 @@ struct DArgs {
     const float* w;    // [Ca][Cb][5][5]
     float* gx;         // fine   [Cb][D][Hf][Wf]
     int D, Hf, Wf, Hc, Wc;
-    int nx, ny, ntiles;
-    int S;
+    wshare::Grid g;   // one block
 };
 
 template <int CB>
@@ -263,10 +211,9 @@ __global__ __launch_bounds__(256, 1) void conv_dgrad_k5s2_kernel(DArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ln = lane & 15, lk = lane >> 4;
-    const int per = (a.S + 7) >> 3;
-    const int s = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (s >= a.S) return;
-    const int t0 = (int)((long)s * a.ntiles / a.S), t1 = (int)((long)(s + 1) * a.ntiles / a.S);
+    const int s = wshare::place(a.g, blockIdx.x);
+    if (s < 0) return;
+    const int t0 = wshare::first_tile(a.g, s), t1 = wshare::first_tile(a.g, s + 1);
     const size_t cplane = (size_t)a.Hc * a.Wc, cvol = cplane * a.D;
     const size_t fplane = (size_t)a.Hf * a.Wf, fvol = fplane * a.D;
 
@@ -284,8 +231,8 @@ __global__ __launch_bounds__(256, 1) void conv_dgrad_k5s2_kernel(DArgs a) {
     }
 
     for (int tile = t0; tile < t1; ++tile) {
-        const int bx = tile % a.nx, rr = tile / a.nx, by = rr % a.ny, z = rr / a.ny;
-        const int i0 = bx * kDI, j0 = by * kDJ;
+        const wshare::Tile t = wshare::decode(a.g, tile);
+        const int i0 = t.bx * kDI, j0 = t.by * kDJ, z = t.z;
         __syncthreads();   // every wave is done reading the previous tile
         for (int i = tid; i < CA * NR * RW; i += 256) {
             const int c = i / (NR * RW), r = i % (NR * RW), y = j0 + r / RW - 1, x = i0 + r % RW - 1;
@@ -358,10 +305,8 @@ __global__ __launch_bounds__(256, 1) void conv_dgrad_k5s2_kernel(DArgs a) {
 }
 
 inline bool dgeometry(int D, int Hf, int Wf, DArgs& a) {
-    if (!tile_grid(D, Hf, Wf, kDJ, kDI, a.Hc, a.Wc, a.nx, a.ny, a.ntiles)) return false;
     a.D = D; a.Hf = Hf; a.Wf = Wf;
-    a.S = a.ntiles < kMaxWg ? a.ntiles : kMaxWg;
-    return true;
+    return tile_grid(D, Hf, Wf, kDJ, kDI, a.Hc, a.Wc, a.g);
 }
 
 template <int CB>
@@ -372,7 +317,7 @@ int dlaunch(const DArgs& a, hipStream_t st) {
     static_assert(G::DS % 32 == 16, "the two k-lanes of a half wave must fall on other banks");
     auto kernel = conv_dgrad_k5s2_kernel<CB>;
     if (int e = dmvs_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
-    kernel<<<dim3(xcd_grid(a.S)), 256, lds, st>>>(a);
+    kernel<<<dim3(xcd_grid(a.g.nwg)), 256, lds, st>>>(a);
     DMVS_LAUNCH_CHECK();
 }
 
@@ -381,14 +326,14 @@ int dlaunch(const DArgs& a, hipStream_t st) {
 extern "C" long dmvs_conv2d_k5s2_wgrad_workspace(int Ca, int D, int Hf, int Wf) {
     k5s2::Args a;
     if (!k5s2::shape_ok(Ca) || !k5s2::geometry(Ca, D, Hf, Wf, a)) return 0;
-    return (long)k5s2::kMaxWg * k5s2::kNT * Ca * (Ca / 2);   // one partial per share, whatever the image
+    return wshare::workspace(1, (long)k5s2::kNT * Ca * (Ca / 2));
 }
 
 extern "C" int dmvs_conv2d_k5s2_wgrad_plan(int Ca, int D, int Hf, int Wf) {
     k5s2::Args a;
     if (!k5s2::shape_ok(Ca)) return DMVS_EUNSUPPORTED;
     if (!k5s2::geometry(Ca, D, Hf, Wf, a)) return DMVS_EINVAL;
-    return a.ntiles * 512 + (int)xcd_grid(a.S);
+    return wshare::plan(a.g);
 }
 
 extern "C" int dmvs_conv2d_k5s2_wgrad(const float* gy, const float* x, float* gw, float* workspace, int Ca, int D, int Hf, int Wf,

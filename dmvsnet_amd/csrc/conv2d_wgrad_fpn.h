@@ -24,18 +24,15 @@
 //   waves    3x3: the 4 waves split the column BLOCKS (1 / 2 / 5 per wave), each walks all 128 pixels of the tile.
 //            1x1: one block, so the waves split the tile's PIXELS (wave w = row w); their four accumulators are added in wave order
 //            through LDS when the share is done.
-//   grid     persistent: S = min(tiles, 256) workgroups, share s walks [s tiles / S, (s + 1) tiles / S) (x fastest, then y, then the
-//            plane), workgroups in xcd_grid order.
-//   sums     three levels in a fixed order, as K3g: a tile is one MFMA chain from zero per wave, the tiles of a share are added to the
-//            running sum in walk order, the partials [S][co][column] are added by the reduce kernel in the order s = 0 .. S - 1 (and
-//            then onto gw / gbias with `accumulate`).  No atomics: bitwise reproducible.
+//   grid, sums   wgrad_share.h, one block: a tile is one MFMA chain from zero per wave, the partials are [S][co][column] and go onto
+//            gw / gbias.
 #pragma once
 #include "conv3d_wgrad.h"
+#include "wgrad_share.h"
 
 namespace wgrad_fpn {
 
 using wgrad::Frag;
-using wgrad::kMaxWg;
 using wgrad::pad_to;
 
 constexpr int kTY = 4, kTX = 32;   // pixel tile of one plane; dmvs_conv2d_wgrad_fpn_plan counts these
@@ -70,8 +67,7 @@ struct Args {
     const float* gy;
     float* ws;
     int D, H, W;
-    int nx, ny, ntiles;   // tile grid: nx * ny * D tiles
-    int S;                // shares = workgroups with work
+    wshare::Grid g;   // one block
 };
 
 template <int CIN, int COUT, int KS, bool BIAS>
@@ -88,10 +84,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_fpn_kernel(Args a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ln = lane % M, lk = lane / M;
-    const int per = (a.S + 7) >> 3;
-    const int s = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (s >= a.S) return;
-    const int t0 = (int)((long)s * a.ntiles / a.S), t1 = (int)((long)(s + 1) * a.ntiles / a.S);
+    const int s = wshare::place(a.g, blockIdx.x);
+    if (s < 0) return;
+    const int t0 = wshare::first_tile(a.g, s), t1 = wshare::first_tile(a.g, s + 1);
     const size_t plane = (size_t)a.H * a.W, vol = plane * a.D;
 
     // the lane's column of each of the wave's blocks: LDS offset of (ci(n), tap(n)); a column or block past the end repeats the last one
@@ -114,15 +109,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_fpn_kernel(Args a) {
             for (int r = 0; r < F::ACC; ++r) run[mb][j][r] = 0.f;
 
     for (int tile = t0; tile < t1; ++tile) {
-        const int bx = tile % a.nx, rr = tile / a.nx, by = rr % a.ny, z = rr / a.ny;
-        const int x0 = bx * kTX, y0 = by * kTY;
+        const wshare::Tile t = wshare::decode(a.g, tile);
+        const int x0 = t.bx * kTX, y0 = t.by * kTY, z = t.z;
         __syncthreads();   // every wave is done reading the previous tile
-        for (int i = tid; i < G::ROWS * kTY * kTX; i += 256) {
-            const int c = i / (kTY * kTX), r = i % (kTY * kTX), y = y0 + r / kTX, x = x0 + r % kTX;
-            float v = 0.f;
-            if (c < COUT && y < a.H && x < a.W) v = a.gy[(size_t)c * vol + z * plane + (size_t)y * a.W + x];
-            dys[c * DYS + r] = v;
-        }
+        wshare::stage_rows<G::ROWS, kTY, kTX>(dys, DYS, a.gy, 0, COUT, vol, plane, z, y0, x0, a.H, a.W, tid);
         for (int i = tid; i < G::XCH * IY * IXP; i += 256) {
             const int c = i / (IY * IXP), r = i % (IY * IXP), y = y0 + r / IXP - H2, x = x0 + r % IXP - H2;
             float v = 0.f;
@@ -203,13 +193,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_fpn_kernel(Args a) {
 // gbias is null).  One thread per element, in workspace order.
 __global__ __launch_bounds__(256) void conv_wgrad_fpn_reduce_kernel(const float* __restrict__ ws, float* __restrict__ gw,
                                                                      float* __restrict__ gbias, int Cout, int NW, int NC, int S, int accumulate) {
-    const int n = Cout * NC, e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    float sum = ws[e];
-    for (int s = 1; s < S; ++s) sum += ws[(size_t)s * n + e];
-    const int co = e / NC, col = e % NC;
-    float* o = col < NW ? gw + (size_t)co * NW + col : (gbias ? gbias + co : nullptr);
-    if (o) *o = accumulate ? *o + sum : sum;
+    wshare::reduce(ws, Cout * NC, S, accumulate, [=](int e) {
+        const int co = e / NC, col = e % NC;
+        return col < NW ? gw + (size_t)co * NW + col : (gbias ? gbias + co : nullptr);
+    });
 }
 
 // the six layers: index into the shape table, -1 for any other shape
@@ -224,14 +211,8 @@ inline int columns_of(const Shape& s) { return s.ks * s.ks * s.cin + s.bias; }
 
 // the launch geometry, one source of truth for the launcher, the workspace size and the plan
 inline bool geometry(int D, int H, int W, Args& a) {
-    if (D < 1 || H < 1 || W < 1) return false;
     a.D = D; a.H = H; a.W = W;
-    a.nx = ceil_div(W, kTX); a.ny = ceil_div(H, kTY);
-    const long nt = (long)a.nx * a.ny * D;
-    if (nt >= (1L << 22)) return false;   // the plan packs the tile count into 22 bits (indices are 64-bit throughout)
-    a.ntiles = (int)nt;
-    a.S = a.ntiles < kMaxWg ? a.ntiles : kMaxWg;
-    return true;
+    return wshare::grid(D, H, W, kTY, kTX, 1, a.g);
 }
 
 template <int CIN, int COUT, int KS, bool BIAS>
@@ -239,12 +220,8 @@ int launch(const Args& a, float* gw, float* gbias, int accumulate, hipStream_t s
     typedef Geom<CIN, COUT, KS, BIAS> G;
     constexpr size_t lds = (size_t)G::LDS_F * sizeof(float);
     static_assert(lds <= 160 * 1024, "the two tiles must fit the 160 KB LDS");
-    auto kernel = conv_wgrad_fpn_kernel<CIN, COUT, KS, BIAS>;
-    if (int e = dmvs_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
-    kernel<<<dim3(xcd_grid(a.S)), 256, lds, st>>>(a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-    conv_wgrad_fpn_reduce_kernel<<<dim3(ceil_div(COUT * G::NC, 256)), 256, 0, st>>>(a.ws, gw, gbias, COUT, G::NW, G::NC, a.S, accumulate);
-    DMVS_LAUNCH_CHECK();
+    return wshare::launch(conv_wgrad_fpn_kernel<CIN, COUT, KS, BIAS>, a, lds, st, conv_wgrad_fpn_reduce_kernel, COUT * G::NC, a.ws, gw, gbias,
+                          COUT, G::NW, G::NC, a.g.S, accumulate);
 }
 
 }  // namespace wgrad_fpn
@@ -253,14 +230,14 @@ extern "C" long dmvs_conv2d_wgrad_fpn_workspace(int Cin, int Cout, int ksize, in
     wgrad_fpn::Args a;
     const wgrad_fpn::Shape* s = wgrad_fpn::find_shape(Cin, Cout, ksize);
     if (!s || !wgrad_fpn::geometry(D, H, W, a)) return 0;
-    return (long)wgrad_fpn::kMaxWg * Cout * wgrad_fpn::columns_of(*s);   // one partial per share, whatever the planes
+    return wshare::workspace(1, (long)Cout * wgrad_fpn::columns_of(*s));
 }
 
 extern "C" int dmvs_conv2d_wgrad_fpn_plan(int Cin, int Cout, int ksize, int D, int H, int W) {
     wgrad_fpn::Args a;
     if (!wgrad_fpn::find_shape(Cin, Cout, ksize)) return DMVS_EUNSUPPORTED;
     if (!wgrad_fpn::geometry(D, H, W, a)) return DMVS_EINVAL;
-    return a.ntiles * 512 + (int)xcd_grid(a.S);
+    return wshare::plan(a.g);
 }
 
 extern "C" int dmvs_conv2d_wgrad_fpn(const float* x, const float* gy, float* gw, float* gbias, float* workspace, int Cin, int Cout, int D,

@@ -16,15 +16,10 @@
 //            tile and owns TPW accumulator blocks (TPW * 16 = 112 registers on the 32-row MFMA, where 27 blocks would not fit).  One
 //            dY fragment feeds TPW MFMAs; a tap is a wave-uniform LDS offset.
 //   blocks   C = 64 has 2 x 2 (co, ci) blocks of 32: a workgroup owns ONE block pair.
-//   grid     persistent: at most 256 workgroups (one per CU), NBP block pairs x S voxel shares, S = min(tiles, 256 / NBP); share s
-//            walks the contiguous tile range [s * tiles / S, (s + 1) * tiles / S) (x fastest, then y, then z; XCD k gets the k-th
-//            eighth of the workgroups, common.h).
-//   sums     three levels, all in a fixed order: a tile's 128 voxels are ONE MFMA chain from zero (128 fmaf); the tiles of a share are
-//            added to the running sum one after the other (VALU adds); the S partials are written to the workspace
-//            [S][tap][co][ci] and a second kernel adds them in the order s = 0 .. S - 1 (and then to gw with `accumulate`).
-//            No atomics anywhere: the result is bitwise reproducible.
+//   grid, sums   wgrad_share.h, with NBP block pairs as the blocks: a tile's 128 voxels are ONE MFMA chain from zero (128 fmaf), the
+//            running sum is VALU adds, the partials are [S][tap][co][ci].
 #pragma once
-#include "common.h"
+#include "wgrad_share.h"
 
 namespace wgrad {
 
@@ -46,7 +41,6 @@ template <> struct Frag<16> {
 };
 
 constexpr int kTY = 4, kTX = 32;   // voxel tile (one z plane); dmvs_conv3d_wgrad_plan counts these
-constexpr int kMaxWg = 256;        // one workgroup per CU
 
 constexpr int pad_to(int n, int want) { return n + ((want - n % 64) + 64) % 64; }   // smallest n' >= n with n' % 64 == want
 
@@ -66,8 +60,7 @@ struct Args {
     const float* gy;
     float* ws;
     int C, D, H, W;
-    int nx, ny, ntiles;   // tile grid: nx * ny * D tiles
-    int S, nwg;           // voxel shares; workgroups with work = S * (C / M)^2
+    wshare::Grid g;   // blocks = (C / M)^2
 };
 
 template <int M, int KD>
@@ -83,13 +76,12 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(Args a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ln = lane % M, lk = lane / M;
-    const int per = (a.nwg + 7) >> 3;
-    const int wg = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (wg >= a.nwg) return;
+    const int wg = wshare::place(a.g, blockIdx.x);
+    if (wg < 0) return;
     const int NB = a.C / M, NBP = NB * NB;
     const int bp = wg % NBP, s = wg / NBP;
     const int co0 = (bp / NB) * M, ci0 = (bp % NB) * M;
-    const int t0 = (int)((long)s * a.ntiles / a.S), t1 = (int)((long)(s + 1) * a.ntiles / a.S);
+    const int t0 = wshare::first_tile(a.g, s), t1 = wshare::first_tile(a.g, s + 1);
     const size_t plane = (size_t)a.H * a.W, vol = plane * a.D;
 
     // the wave's taps wave * TPW + j; a tap past the end repeats the last one (computed, never written)
@@ -108,15 +100,10 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(Args a) {
         for (int r = 0; r < F::ACC; ++r) run[j][r] = 0.f;
 
     for (int tile = t0; tile < t1; ++tile) {
-        const int bx = tile % a.nx, rr = tile / a.nx, by = rr % a.ny, z = rr / a.ny;
-        const int x0 = bx * kTX, y0 = by * kTY;
+        const wshare::Tile t = wshare::decode(a.g, tile);
+        const int x0 = t.bx * kTX, y0 = t.by * kTY, z = t.z;
         __syncthreads();   // every wave is done reading the previous tile
-        for (int i = tid; i < M * kTY * kTX; i += 256) {
-            const int c = i / (kTY * kTX), r = i % (kTY * kTX), y = y0 + r / kTX, x = x0 + r % kTX;
-            float v = 0.f;
-            if (y < a.H && x < a.W) v = a.gy[(size_t)(co0 + c) * vol + z * plane + (size_t)y * a.W + x];
-            dys[c * DYS + r] = v;
-        }
+        wshare::stage_rows<M, kTY, kTX>(dys, DYS, a.gy, co0, M, vol, plane, z, y0, x0, a.H, a.W, tid);
         for (int i = tid; i < M * KD * IY * IXP; i += 256) {
             const int c = i / (KD * IY * IXP), r = i % (KD * IY * IXP);
             const int pz = r / (IY * IXP), py = (r / IXP) % IY, px = r % IXP;
@@ -167,13 +154,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(Args a) {
 // gw[co][ci][tap] (+)= sum_{s = 0 .. S-1} ws[s][tap][co][ci], s ascending.  One thread per element, in workspace order.
 __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ gw, int C, int NT, int S,
                                                                  int accumulate) {
-    const int n = NT * C * C, e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    float sum = ws[e];
-    for (int s = 1; s < S; ++s) sum += ws[(size_t)s * n + e];
-    const int t = e / (C * C), co = (e / C) % C, ci = e % C;
-    float* o = gw + ((size_t)co * C + ci) * NT + t;
-    *o = accumulate ? *o + sum : sum;
+    wshare::reduce(ws, NT * C * C, S, accumulate, [=](int e) { return wshare::tap_last(gw, e, C, C, NT); });
 }
 
 inline bool shape_ok(int C, int kdepth) { return (C == 16 || C == 32 || C == 64) && (kdepth == 1 || kdepth == 3); }
@@ -181,16 +162,8 @@ inline int blocks_of(int C) { return C == 64 ? 4 : 1; }   // (co, ci) block pair
 
 // the launch geometry, one source of truth for the launcher, the workspace size and the plan
 inline bool geometry(int C, int D, int H, int W, Args& a) {
-    if (D < 1 || H < 1 || W < 1) return false;
     a.C = C; a.D = D; a.H = H; a.W = W;
-    a.nx = ceil_div(W, kTX); a.ny = ceil_div(H, kTY);
-    const long nt = (long)a.nx * a.ny * D;
-    if (nt >= (1L << 22)) return false;   // the plan packs the tile count into 22 bits (indices are 64-bit throughout)
-    a.ntiles = (int)nt;
-    const int smax = kMaxWg / blocks_of(C);
-    a.S = a.ntiles < smax ? a.ntiles : smax;
-    a.nwg = a.S * blocks_of(C);
-    return true;
+    return wshare::grid(D, H, W, kTY, kTX, blocks_of(C), a.g);
 }
 
 template <int M, int KD>
@@ -198,13 +171,8 @@ int launch(const Args& a, float* gw, int accumulate, hipStream_t st) {
     typedef Geom<M, KD> G;
     constexpr size_t lds = (size_t)G::LDS_F * sizeof(float);
     static_assert(lds <= 160 * 1024, "the two tiles must fit the 160 KB LDS");
-    auto kernel = conv_wgrad_kernel<M, KD>;
-    if (int e = dmvs_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
-    kernel<<<dim3(xcd_grid(a.nwg)), 256, lds, st>>>(a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-    const int n = G::NT * a.C * a.C;
-    conv_wgrad_reduce_kernel<<<dim3(ceil_div(n, 256)), 256, 0, st>>>(a.ws, gw, a.C, G::NT, a.S, accumulate);
-    DMVS_LAUNCH_CHECK();
+    return wshare::launch(conv_wgrad_kernel<M, KD>, a, lds, st, conv_wgrad_reduce_kernel, G::NT * a.C * a.C, a.ws, gw, a.C, G::NT, a.g.S,
+                          accumulate);
 }
 
 }  // namespace wgrad
@@ -212,14 +180,14 @@ int launch(const Args& a, float* gw, int accumulate, hipStream_t st) {
 extern "C" long dmvs_conv3d_wgrad_workspace(int C, int D, int H, int W, int kdepth) {
     wgrad::Args a;
     if (!wgrad::shape_ok(C, kdepth) || !wgrad::geometry(C, D, H, W, a)) return 0;
-    return (long)(wgrad::kMaxWg / wgrad::blocks_of(C)) * 9 * kdepth * C * C;   // one partial per voxel share, whatever the volume
+    return wshare::workspace(wgrad::blocks_of(C), 9L * kdepth * C * C);
 }
 
 extern "C" int dmvs_conv3d_wgrad_plan(int C, int D, int H, int W, int kdepth) {
     wgrad::Args a;
     if (!wgrad::shape_ok(C, kdepth)) return DMVS_EUNSUPPORTED;
     if (!wgrad::geometry(C, D, H, W, a)) return DMVS_EINVAL;
-    return a.ntiles * 512 + (int)xcd_grid(a.nwg);
+    return wshare::plan(a.g);
 }
 
 extern "C" int dmvs_conv3d_wgrad(const float* x, const float* gy, float* gw, float* workspace, int C, int D, int H, int W, int kdepth,

@@ -21,19 +21,15 @@
 //   waves    the 4 waves of a workgroup split the 27 TAPS (7 + 7 + 7 + 6), as K3g does: every wave walks all voxels of the tile, a row
 //            of 64 per step, and a lane owns 7 x 8 x 2 = 112 accumulators.  Per row: 8 LDS reads of P, then per tap 2 reads of Q (a tap
 //            is a wave-uniform LDS offset) feeding 16 fmaf.
-//   grid     persistent: at most 256 workgroups (one per CU), S = min(tiles, 256) voxel shares; share s walks the contiguous tile range
-//            [s * tiles / S, (s + 1) * tiles / S) (x fastest, then y, then z; XCD k gets the k-th eighth of the workgroups, common.h).
-//   sums     all in a fixed order: a lane adds its voxel of every row of every tile of the share to its running sums in walk order
-//            (one fmaf chain per accumulator); at the end of the share the 64 lanes are folded ONCE by a butterfly over lane ^ 32, 16,
-//            .. 1 (both partners form the same a + b); the S partials go to the workspace [S][tap][p][q] and a second kernel adds
-//            them in the order s = 0 .. S - 1 (and then to gw with `accumulate`).  No atomics anywhere: bitwise reproducible.
+//   grid, sums   wgrad_share.h, one block.  Within a share a lane adds its voxel of every row of every tile to its running sums in walk
+//            order (one fmaf chain per accumulator); at the end of the share the 64 lanes are folded ONCE by a butterfly over
+//            lane ^ 32, 16, .. 1 (both partners form the same a + b).  The partials are [S][tap][p][q].
 #pragma once
-#include "common.h"
+#include "wgrad_share.h"
 
 namespace wgrad_c2 {
 
 constexpr int kTY = 4, kTX = 64;   // voxel tile (one z plane); dmvs_conv3d_wgrad_c2_plan counts these
-constexpr int kMaxWg = 256;        // one workgroup per CU
 constexpr int kP = 8, kQ = 2, kNT = 27, kTPW = 7;   // channels of P and Q, taps, taps per wave
 constexpr int kG = kNT * kP * kQ;                   // 432 outputs
 constexpr int kIY = kTY + 2, kIXP = kTX + 2;
@@ -47,8 +43,7 @@ struct Args {
     const float* q;   // [2][D][H][W]
     float* ws;
     int D, H, W;
-    int nx, ny, ntiles;   // tile grid: nx * ny * D tiles
-    int S, nwg;           // voxel shares = workgroups with work
+    wshare::Grid g;   // one block
 };
 
 struct Staged {
@@ -60,8 +55,8 @@ struct Staged {
 // formed outside the two tensors); which of them are inside goes into a bit mask, and the zero is selected only when the value is
 // stored to LDS (store_tile): nothing between the 18 loads of a thread and the arithmetic waits for them
 __device__ __forceinline__ void load_tile(const Args& a, int tile, int tid, Staged& r) {
-    const int bx = tile % a.nx, rr = tile / a.nx, by = rr % a.ny, z = rr / a.ny;
-    const int x0 = bx * kTX, y0 = by * kTY;
+    const wshare::Tile t = wshare::decode(a.g, tile);
+    const int x0 = t.bx * kTX, y0 = t.by * kTY, z = t.z;
     const size_t plane = (size_t)a.H * a.W, vol = plane * a.D;
     {
         const int y = y0 + tid / kTX, x = x0 + tid % kTX;
@@ -97,10 +92,9 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_c2_kernel(Args a) {
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int per = (a.nwg + 7) >> 3;
-    const int s = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (s >= a.nwg) return;
-    const int t0 = (int)((long)s * a.ntiles / a.S), t1 = (int)((long)(s + 1) * a.ntiles / a.S);
+    const int s = wshare::place(a.g, blockIdx.x);
+    if (s < 0) return;
+    const int t0 = wshare::first_tile(a.g, s), t1 = wshare::first_tile(a.g, s + 1);
 
     // the wave's taps wave * 7 + j; the 28th repeats the 27th (computed, never written)
     int toff[kTPW];
@@ -161,28 +155,18 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_c2_kernel(Args a) {
 // gw (+)= sum_{s = 0 .. S-1} ws[s][tap][p][q], s ascending, through the role map: conv0 (prob == 0) gw[p][q][t], prob gw[q][p][26 - t].
 __global__ __launch_bounds__(256) void conv_wgrad_c2_reduce_kernel(const float* __restrict__ ws, float* __restrict__ gw, int S, int prob,
                                                                     int accumulate) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= kG) return;
-    float sum = ws[e];
-    for (int s = 1; s < S; ++s) sum += ws[(size_t)s * kG + e];
-    const int t = e / (kP * kQ), p = (e / kQ) % kP, q = e % kQ;
-    float* o = gw + (prob ? (q * kP + p) * kNT + (kNT - 1 - t) : (p * kQ + q) * kNT + t);
-    *o = accumulate ? *o + sum : sum;
+    wshare::reduce(ws, kG, S, accumulate, [=](int e) {
+        const int t = e / (kP * kQ), p = (e / kQ) % kP, q = e % kQ;
+        return gw + (prob ? (q * kP + p) * kNT + (kNT - 1 - t) : (p * kQ + q) * kNT + t);
+    });
 }
 
 inline bool shape_ok(int Cin, int Cout) { return (Cin == 2 && Cout == 8) || (Cin == 8 && Cout == 2); }
 
 // the launch geometry, one source of truth for the launcher, the workspace size and the plan
 inline bool geometry(int D, int H, int W, Args& a) {
-    if (D < 1 || H < 1 || W < 1) return false;
     a.D = D; a.H = H; a.W = W;
-    a.nx = ceil_div(W, kTX); a.ny = ceil_div(H, kTY);
-    const long nt = (long)a.nx * a.ny * D;
-    if (nt >= (1L << 22)) return false;   // the plan packs the tile count into 22 bits (indices are 64-bit throughout)
-    a.ntiles = (int)nt;
-    a.S = a.ntiles < kMaxWg ? a.ntiles : kMaxWg;
-    a.nwg = a.S;
-    return true;
+    return wshare::grid(D, H, W, kTY, kTX, 1, a.g);
 }
 
 }  // namespace wgrad_c2
@@ -190,14 +174,14 @@ inline bool geometry(int D, int H, int W, Args& a) {
 extern "C" long dmvs_conv3d_wgrad_c2_workspace(int Cin, int Cout, int D, int H, int W) {
     wgrad_c2::Args a;
     if (!wgrad_c2::shape_ok(Cin, Cout) || !wgrad_c2::geometry(D, H, W, a)) return 0;
-    return (long)wgrad_c2::kMaxWg * wgrad_c2::kG;   // one partial per voxel share, whatever the volume
+    return wshare::workspace(1, wgrad_c2::kG);
 }
 
 extern "C" int dmvs_conv3d_wgrad_c2_plan(int Cin, int Cout, int D, int H, int W) {
     wgrad_c2::Args a;
     if (!wgrad_c2::shape_ok(Cin, Cout)) return DMVS_EUNSUPPORTED;
     if (!wgrad_c2::geometry(D, H, W, a)) return DMVS_EINVAL;
-    return a.ntiles * 512 + (int)xcd_grid(a.nwg);
+    return wshare::plan(a.g);
 }
 
 extern "C" int dmvs_conv3d_wgrad_c2(const float* x, const float* gy, float* gw, float* workspace, int Cin, int Cout, int D, int H, int W,
@@ -209,8 +193,6 @@ extern "C" int dmvs_conv3d_wgrad_c2(const float* x, const float* gy, float* gw, 
     const int prob = Cin == 8;   // P is the 8-channel tensor, Q the 2-channel one
     a.p = prob ? x : gy; a.q = prob ? gy : x; a.ws = workspace;
     hipStream_t st = (hipStream_t)stream;
-    wgrad_c2::conv_wgrad_c2_kernel<<<dim3(xcd_grid(a.nwg)), 256, 0, st>>>(a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-    wgrad_c2::conv_wgrad_c2_reduce_kernel<<<dim3(ceil_div(wgrad_c2::kG, 256)), 256, 0, st>>>(workspace, gw, a.S, prob, accumulate ? 1 : 0);
-    DMVS_LAUNCH_CHECK();
+    return wshare::launch(wgrad_c2::conv_wgrad_c2_kernel, a, 0, st, wgrad_c2::conv_wgrad_c2_reduce_kernel, wgrad_c2::kG, workspace, gw,
+                          a.g.S, prob, accumulate ? 1 : 0);   // (static LDS)
 }

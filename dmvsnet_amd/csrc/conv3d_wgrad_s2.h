@@ -23,18 +23,15 @@
 //   banks    ds_read_b32: 32 banks, the two 32-lane halves of a wave are served separately.  docs/kernels/K3h_conv_wgrad_s2.md
 //            derives the strides (FS, AS, RS, OB below) that put the 32 lanes of a half on 32 different banks for every slot.
 //   waves    the 4 waves of a workgroup split the slots (4 + 4 + 4 + 2 of 14, 7 + 7 + 7 + 6 of 27, 3 + 3 + 3 + 0 of 9).
-//   grid     persistent: at most 256 workgroups, NB a-blocks x S voxel shares, S = min(tiles, 256 / NB), share s walks the tile range
-//            [s * tiles / S, (s + 1) * tiles / S) (x fastest, then y, then z), workgroups in xcd_grid order (common.h).
-//   sums     three levels in a fixed order, as K3g: a tile is one MFMA chain from zero, the tiles of a share are added to a running
-//            sum one after the other, the S partials go to the workspace [S][tap][a][b] and a second kernel adds them in the order
-//            s = 0 .. S - 1 (and then to gw with `accumulate`).  No atomics: the result is bitwise reproducible.
+//   grid, sums   wgrad_share.h, with the NB a-blocks as the blocks; a tile is one MFMA chain from zero, the partials are [S][tap][a][b].
+//            The chain and the partial store (tile_chain, store_partial) are K3k's too.
 #pragma once
 #include "conv3d_wgrad.h"
+#include "wgrad_share.h"
 
 namespace wgrad_s2 {
 
 using wgrad::Frag;
-using wgrad::kMaxWg;
 
 constexpr int kTX = 32;
 
@@ -79,9 +76,46 @@ struct Args {
     const float* fine;
     float* ws;
     int Ca, Cb, Dc, Hc, Wc;
-    int nx, ny, ntiles;   // tile grid: nx * ny * Dc tiles
-    int S, nwg;           // voxel shares; workgroups with work = S * (Ca / MF)
+    wshare::Grid g;   // blocks = Ca / MF
 };
+
+// one tile of K3h / K3k: an MFMA chain from zero over its TY x 32 coarse voxels per slot, then added to the share's running sums.
+// pa: the lane's A fragment in the coarse tile; pb[j]: the lane's tap of slot j in the parity-split fine halo (row stride RS)
+template <int MF, int SPW, int TY, int RS>
+__device__ __forceinline__ void tile_chain(const float* pa, const float* (&pb)[SPW], typename Frag<MF>::acc_t (&run)[SPW]) {
+    typedef Frag<MF> F;
+    constexpr int KK = F::KK, TX = kTX;
+    typename F::acc_t acc[SPW];
+#pragma unroll
+    for (int j = 0; j < SPW; ++j)
+#pragma unroll
+        for (int r = 0; r < F::ACC; ++r) acc[j][r] = 0.f;
+#pragma unroll 1
+    for (int y = 0; y < TY; ++y) {
+#pragma unroll
+        for (int g = 0; g < TX / KK; ++g) {
+            const float av = pa[y * TX + g * KK];
+#pragma unroll
+            for (int j = 0; j < SPW; ++j) acc[j] = F::mfma(av, pb[j][2 * y * RS + g * KK], acc[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < SPW; ++j) run[j] += acc[j];
+}
+
+// partial of a share: w[tap][a][b]; the CB lanes of a tap's row write CB contiguous floats
+template <int MF, int CB, int SPW>
+__device__ __forceinline__ void store_partial(float* w, int Ca, int a0, int lk, int lb, const int (&tap)[SPW],
+                                              const typename Frag<MF>::acc_t (&run)[SPW]) {
+    typedef Frag<MF> F;
+#pragma unroll
+    for (int j = 0; j < SPW; ++j) {
+        if (tap[j] >= 0) {
+#pragma unroll
+            for (int r = 0; r < F::ACC; ++r) w[((size_t)tap[j] * Ca + a0 + F::row(r, lk)) * CB + lb] = run[j][r];
+        }
+    }
+}
 
 template <int MF, int CB, int KD>
 __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(Args a) {
@@ -89,7 +123,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(Args a) {
     typedef typename F::acc_t acc_t;
     typedef Geom<MF, CB, KD> G;
     constexpr int NT = G::NT, NP = G::NP, SPW = G::SPW, TPN = G::TPN, TY = G::TY, IY = G::IY, OB = G::OB, RS = G::RS, FS = G::FS,
-                  AS = G::AS, KK = G::KK, TX = kTX;
+                  AS = G::AS, TX = kTX;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* fs = smem;
     float* as = smem + CB * FS;
@@ -98,13 +132,12 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(Args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ln = lane % MF, lk = lane / MF;
     const int lq = ln / CB, lb = ln % CB;   // this lane's half of the slot and its fine channel
-    const int per = (a.nwg + 7) >> 3;
-    const int wg = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (wg >= a.nwg) return;
+    const int wg = wshare::place(a.g, blockIdx.x);
+    if (wg < 0) return;
     const int NB = a.Ca / MF;
     const int blk = wg % NB, s = wg / NB;
     const int a0 = blk * MF;
-    const int t0 = (int)((long)s * a.ntiles / a.S), t1 = (int)((long)(s + 1) * a.ntiles / a.S);
+    const int t0 = wshare::first_tile(a.g, s), t1 = wshare::first_tile(a.g, s + 1);
     const int Hf = 2 * a.Hc, Wf = 2 * a.Wc, Df = KD == 3 ? 2 * a.Dc : a.Dc;
     const size_t cplane = (size_t)a.Hc * a.Wc, cvol = cplane * a.Dc;
     const size_t fplane = (size_t)Hf * Wf, fvol = fplane * Df;
@@ -131,15 +164,10 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(Args a) {
         for (int r = 0; r < F::ACC; ++r) run[j][r] = 0.f;
 
     for (int tile = t0; tile < t1; ++tile) {
-        const int bx = tile % a.nx, rr = tile / a.nx, by = rr % a.ny, z = rr / a.ny;
-        const int x0 = bx * TX, y0 = by * TY;
+        const wshare::Tile t = wshare::decode(a.g, tile);
+        const int x0 = t.bx * TX, y0 = t.by * TY, z = t.z;
         __syncthreads();   // every wave is done reading the previous tile
-        for (int i = tid; i < MF * TY * TX; i += 256) {
-            const int c = i / (TY * TX), r = i % (TY * TX), y = y0 + r / TX, x = x0 + r % TX;
-            float v = 0.f;
-            if (y < a.Hc && x < a.Wc) v = a.coarse[(size_t)(a0 + c) * cvol + z * cplane + (size_t)y * a.Wc + x];
-            as[c * AS + r] = v;
-        }
+        wshare::stage_rows<MF, TY, TX>(as, AS, a.coarse, a0, MF, cvol, cplane, z, y0, x0, a.Hc, a.Wc, tid);
         // the fine halo: columns 2 x0 - 1 .. 2 x0 + 2 TX - 1 of rows 2 y0 - 1 .. 2 y0 + 2 TY - 1 of planes 2z - 1 .. 2z + 1 (kdepth 1: z),
         // read along x and written split by parity: column 2 (x0 + i) -> [i], column 2 (x0 + i) - 1 -> [OB + i]
         constexpr int FW = 2 * TX + 1;
@@ -153,51 +181,15 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(Args a) {
             fs[c * FS + (pz * IY + py) * RS + ((f & 1) ? (f >> 1) : OB + (f >> 1))] = v;
         }
         __syncthreads();
-        if (live) {
-            acc_t acc[SPW];
-#pragma unroll
-            for (int j = 0; j < SPW; ++j)
-#pragma unroll
-                for (int r = 0; r < F::ACC; ++r) acc[j][r] = 0.f;
-            const float* pa = as + ln * AS + lk;
-#pragma unroll 1
-            for (int y = 0; y < TY; ++y) {
-#pragma unroll
-                for (int g = 0; g < TX / KK; ++g) {
-                    const float av = pa[y * TX + g * KK];
-#pragma unroll
-                    for (int j = 0; j < SPW; ++j) acc[j] = F::mfma(av, pb[j][2 * y * RS + g * KK], acc[j]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SPW; ++j) run[j] += acc[j];
-        }
+        if (live) tile_chain<MF, SPW, TY, RS>(as + ln * AS + lk, pb, run);
     }
-
-    // partial of this share: ws[s][tap][a][b]; the CB lanes of a tap's row write CB contiguous floats
-    if (live) {
-        float* w = a.ws + (size_t)s * NT * a.Ca * CB;
-#pragma unroll
-        for (int j = 0; j < SPW; ++j) {
-            if (tap[j] >= 0) {
-#pragma unroll
-                for (int r = 0; r < F::ACC; ++r)
-                    w[((size_t)tap[j] * a.Ca + a0 + F::row(r, lk)) * CB + lb] = run[j][r];
-            }
-        }
-    }
+    if (live) store_partial<MF, CB, SPW>(a.ws + (size_t)s * NT * a.Ca * CB, a.Ca, a0, lk, lb, tap, run);
 }
 
 // gw[a][b][tap] (+)= sum_{s = 0 .. S-1} ws[s][tap][a][b], s ascending.  One thread per element, in workspace order.
 __global__ __launch_bounds__(256) void conv_wgrad_s2_reduce_kernel(const float* __restrict__ ws, float* __restrict__ gw, int Ca, int Cb,
                                                                     int NT, int S, int accumulate) {
-    const int n = NT * Ca * Cb, e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= n) return;
-    float sum = ws[e];
-    for (int s = 1; s < S; ++s) sum += ws[(size_t)s * n + e];
-    const int t = e / (Ca * Cb), ca = (e / Cb) % Ca, cb = e % Cb;
-    float* o = gw + ((size_t)ca * Cb + cb) * NT + t;
-    *o = accumulate ? *o + sum : sum;
+    wshare::reduce(ws, NT * Ca * Cb, S, accumulate, [=](int e) { return wshare::tap_last(gw, e, Ca, Cb, NT); });
 }
 
 inline bool shape_ok(int Ca, int kdepth) { return kdepth == 3 ? (Ca == 16 || Ca == 32 || Ca == 64) : (kdepth == 1 && Ca == 64); }
@@ -206,17 +198,9 @@ inline int tile_rows(int Ca, int kdepth) { return Ca == 64 && kdepth == 3 ? 2 : 
 
 // the launch geometry, one source of truth for the launcher, the workspace size and the plan
 inline bool geometry(int Ca, int Dc, int Hc, int Wc, int kdepth, Args& a) {
-    if (Dc < 1 || Hc < 1 || Wc < 1) return false;
     if (Hc > (1 << 20) || Wc > (1 << 20) || Dc > (1 << 20)) return false;   // 2 * extent stays an int
     a.Ca = Ca; a.Cb = Ca / 2; a.Dc = Dc; a.Hc = Hc; a.Wc = Wc;
-    a.nx = ceil_div(Wc, kTX); a.ny = ceil_div(Hc, tile_rows(Ca, kdepth));
-    const long nt = (long)a.nx * a.ny * Dc;
-    if (nt >= (1L << 22)) return false;   // the plan packs the tile count into 22 bits (indices are 64-bit throughout)
-    a.ntiles = (int)nt;
-    const int smax = kMaxWg / blocks_of(Ca);
-    a.S = a.ntiles < smax ? a.ntiles : smax;
-    a.nwg = a.S * blocks_of(Ca);
-    return true;
+    return wshare::grid(Dc, Hc, Wc, tile_rows(Ca, kdepth), kTX, blocks_of(Ca), a.g);
 }
 
 template <int MF, int CB, int KD>
@@ -224,13 +208,8 @@ int launch(const Args& a, float* gw, int accumulate, hipStream_t st) {
     typedef Geom<MF, CB, KD> G;
     constexpr size_t lds = (size_t)G::LDS_F * sizeof(float);
     static_assert(lds <= 160 * 1024, "the two tiles must fit the 160 KB LDS");
-    auto kernel = conv_wgrad_s2_kernel<MF, CB, KD>;
-    if (int e = dmvs_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
-    kernel<<<dim3(xcd_grid(a.nwg)), 256, lds, st>>>(a);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-    const int n = G::NT * a.Ca * a.Cb;
-    conv_wgrad_s2_reduce_kernel<<<dim3(ceil_div(n, 256)), 256, 0, st>>>(a.ws, gw, a.Ca, a.Cb, G::NT, a.S, accumulate);
-    DMVS_LAUNCH_CHECK();
+    return wshare::launch(conv_wgrad_s2_kernel<MF, CB, KD>, a, lds, st, conv_wgrad_s2_reduce_kernel, G::NT * a.Ca * a.Cb, a.ws, gw, a.Ca,
+                          a.Cb, G::NT, a.g.S, accumulate);
 }
 
 }  // namespace wgrad_s2
@@ -238,14 +217,14 @@ int launch(const Args& a, float* gw, int accumulate, hipStream_t st) {
 extern "C" long dmvs_conv3d_wgrad_s2_workspace(int Ca, int Dc, int Hc, int Wc, int kdepth) {
     wgrad_s2::Args a;
     if (!wgrad_s2::shape_ok(Ca, kdepth) || !wgrad_s2::geometry(Ca, Dc, Hc, Wc, kdepth, a)) return 0;
-    return (long)(wgrad_s2::kMaxWg / wgrad_s2::blocks_of(Ca)) * 9 * kdepth * Ca * (Ca / 2);   // one partial per share, whatever the volume
+    return wshare::workspace(wgrad_s2::blocks_of(Ca), 9L * kdepth * Ca * (Ca / 2));
 }
 
 extern "C" int dmvs_conv3d_wgrad_s2_plan(int Ca, int Dc, int Hc, int Wc, int kdepth) {
     wgrad_s2::Args a;
     if (!wgrad_s2::shape_ok(Ca, kdepth)) return DMVS_EUNSUPPORTED;
     if (!wgrad_s2::geometry(Ca, Dc, Hc, Wc, kdepth, a)) return DMVS_EINVAL;
-    return a.ntiles * 512 + (int)xcd_grid(a.nwg);
+    return wshare::plan(a.g);
 }
 
 extern "C" int dmvs_conv3d_wgrad_s2(const float* coarse, const float* fine, float* gw, float* workspace, int Ca, int Dc, int Hc, int Wc,

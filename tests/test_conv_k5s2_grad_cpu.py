@@ -136,6 +136,8 @@ def test_c_abi_and_sources():
     src = open(os.path.join(ROOT, "dmvsnet_amd", "csrc", "conv2d_k5s2_bwd.h")).read()
     assert set(re.findall(r"__global__[^;{]*?void\s+(\w+)\s*\(", src)) == KERNELS
     assert "atomic" not in src.lower()
+    shared = open(os.path.join(ROOT, "dmvsnet_amd", "csrc", "wgrad_share.h")).read()
+    assert "atomic" not in shared.lower().replace("no atomics", "")
     doc = open(os.path.join(ROOT, "docs", "kernels", "K3k_conv_wgrad_k5s2.md")).read()
     assert set(re.findall(r"`(conv_\w+_kernel)`", doc)) == KERNELS
     text = open(os.path.join(ROOT, "scripts", "pmc_summary.py")).read()

@@ -199,6 +199,8 @@ def test_c_abi_and_sources():
     src = open(os.path.join(ROOT, "dmvsnet_amd", "csrc", "conv2d_wgrad_fpn.h")).read()
     assert set(re.findall(r"__global__[^;{]*?void\s+(\w+)\s*\(", src)) == KERNELS
     assert "atomic" not in src.lower().replace("no atomics", "")
+    shared = open(os.path.join(ROOT, "dmvsnet_amd", "csrc", "wgrad_share.h")).read()
+    assert "atomic" not in shared.lower().replace("no atomics", "")
     doc = open(os.path.join(ROOT, "docs", "kernels", "K3f_conv_wgrad_fpn.md")).read()
     assert set(re.findall(r"`(conv_\w+_kernel)`", doc)) == KERNELS
     direct = open(os.path.join(ROOT, "dmvsnet_amd", "csrc", "conv3d_direct.hip")).read()

@@ -180,6 +180,8 @@ def test_abi_agreement():
     src = open(os.path.join(ROOT, "dmvsnet_amd", "csrc", "conv3d_wgrad_c2.h")).read()
     assert set(re.findall(r"__global__[^;{]*?void\s+(\w+)\s*\(", src)) == {"conv_wgrad_c2_kernel", "conv_wgrad_c2_reduce_kernel"}
     assert "atomic" not in src.lower().replace("no atomics", "")
+    shared = open(os.path.join(ROOT, "dmvsnet_amd", "csrc", "wgrad_share.h")).read()
+    assert "atomic" not in shared.lower().replace("no atomics", "")
     assert '#include "conv3d_wgrad_c2.h"' in open(os.path.join(ROOT, "dmvsnet_amd", "csrc", "conv3d_direct.hip")).read()
 
 
