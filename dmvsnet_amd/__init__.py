@@ -17,7 +17,7 @@ from .conv import DiffConv2d, DiffConv3d, DiffConvTranspose2d, DiffConvTranspose
 
 from . import bn  # noqa: F401  (differentiable BatchNorm + ReLU: K5 forward / backward, and the four U-Net blocks on it)
 from .bn import (DiffBatchNormReLU2d, DiffBatchNormReLU3d, DiffConvBlock2d, DiffConvBlock3d, DiffDeconvBlock2d,  # noqa: F401
-                 DiffDeconvBlock3d)
+                 DiffDeconvBlock3d, DiffSyncBatchNormReLU2d, DiffSyncBatchNormReLU3d, convert_sync_batchnorm)
 
 from . import regnet  # noqa: F401  (the four regularisation networks on the differentiable layers; conv0 / prob: K2 + K2g)
 from .regnet import DiffCostRegNet, DiffCostRegNetPart, DiffCostRegNetPartRefine, DiffCostRegNetRefine  # noqa: F401
@@ -36,6 +36,7 @@ __all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFea
            "cloud_eval", "reduce_points", "max_dist_cp", "point_compare", "scan_stats", "evaluate_dtu", "validate", "mvs_loss",
            "AbsDepthError_metrics", "Thres_metrics", "DTUValDataset", "run_validate", "DiffCostAgg", "cost_agg", "head", "DiffDepthNet",
            "diff_mvs_loss", "conv", "DiffConv3d", "DiffConv2d", "DiffConvTranspose3d",
-           "DiffConvTranspose2d", "bn", "DiffBatchNormReLU3d", "DiffBatchNormReLU2d", "DiffConvBlock3d", "DiffDeconvBlock3d",
+           "DiffConvTranspose2d", "bn", "DiffBatchNormReLU3d", "DiffBatchNormReLU2d", "DiffSyncBatchNormReLU3d",
+           "DiffSyncBatchNormReLU2d", "convert_sync_batchnorm", "DiffConvBlock3d", "DiffDeconvBlock3d",
            "DiffConvBlock2d", "DiffDeconvBlock2d", "regnet", "DiffCostRegNetPart", "DiffCostRegNetPartRefine", "DiffCostRegNet",
            "DiffCostRegNetRefine", "featurenet", "DiffFeatureConv2d", "DiffFeatureConvBlock2d", "DiffFeatureNet"]

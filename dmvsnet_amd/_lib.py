@@ -109,6 +109,10 @@ SIGNATURES = {
     "dmvs_bn_workspace": (ctypes.c_long, [_i, _i, _i]),
     "dmvs_bn_plan": (_i, [_i, _i, _i]),
     "dmvs_bn_share_range": (_i, [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_long)]),
+    "dmvs_bn_sync_moments": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "dmvs_bn_sync_forward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.POINTER(ctypes.c_long), _i, _i, _i, _i, _f, _f, _i, _p]),
+    "dmvs_bn_sync_backward_sums": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "dmvs_bn_sync_backward_apply": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, ctypes.c_long, _i, _p]),
 }
 
 EINVAL, EUNSUPPORTED = -1, -2   # include/dmvs.h

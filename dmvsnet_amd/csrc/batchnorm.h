@@ -28,6 +28,16 @@
 //   sums       thread: 4 independent fp32 chains (one per vector slot), each as long as the share's chunks (at most
 //              ceil(chunks / S)) ; then ((a0 + a1) + (a2 + a3)); wave: a 6-level butterfly; workgroup: (w0 + w1) + (w2 + w3); partials:
 //              fp64, sequential.  Nothing is exchanged between workgroups inside a launch; nothing is atomic: same input, same bits.
+//   sync       statistics over R ranks (torch.nn.SyncBatchNorm's semantics), one more fold level in the same style; the collectives
+//              themselves are the host's (kernel and entries: batchnorm_sync.h).  bn_stats_kernel as above, then bn_moments_kernel
+//              (C workgroups) folds the S partials and
+//              writes the rank's (n_r, mean_r = p + f0 / n_r, M2_r = f1 - f0^2 / n_r) in fp64: ranks have different pivots, so
+//              MOMENTS travel, never raw sums.  bn_apply_kernel<VEC, true>: the prologue combines the gathered [R][C][3] triples in
+//              the order r = 0 .. R-1 in fp64 (combine() below: N = sum n_r, mean = sum n_r mean_r / N,
+//              M2 = sum (M2_r + n_r (mean_r - mean)^2), var = M2 / N), the same chain in every thread of every workgroup of the channel
+//              on every rank: mean / invstd and the running buffers are the same bits on all ranks.  Backward: bn_bwd_reduce_kernel
+//              on the global mean / invstd, bn_bwd_fold_kernel<true> stores g_beta / g_gamma (the LOCAL sums) and the fp64 pair,
+//              bn_bwd_apply_kernel<VEC, true> adds the gathered [R][C][2] pairs in rank order and divides by the global N.
 #pragma once
 #include "common.h"
 
@@ -37,6 +47,7 @@ constexpr int kLanes = 256, kChunk = 4 * kLanes;   // a chunk: 256 lanes x 16 by
 constexpr int kMaxWg = 2048;                       // C * Smax workgroups: 8 per CU
 constexpr int kUnroll = 4;                         // loads in flight per lane
 constexpr int kPivot = 256;                        // elements behind the pivot
+constexpr int kMaxRanks = 16;                      // ranks whose statistics the sync kernels combine
 
 inline bool channels_ok(int C) { return C == 8 || C == 16 || C == 32 || C == 64; }
 
@@ -73,6 +84,11 @@ struct Args {
     long n;                // B * V
     float momentum, eps;
     int relu, train;
+    // sync kernels only
+    const double* gathered;  // forward: [R][C][3] (n_r, mean_r, M2_r); backward: [R][C][2] (sum g, sum g * xhat)
+    double* dout;            // this rank's [C][3] moments / [C][2] sums
+    double N;                // backward: the global count
+    int R;
 };
 
 // ---- the one statement of the pre-activation: forward apply and backward mask both call it on the same fp32 constants
@@ -183,14 +199,47 @@ __device__ __forceinline__ void fold(const Args& a, int c, double* part /* [2 * 
     for (int s = 0; s < a.S; ++s) { f0 += part[2 * s]; f1 += part[2 * s + 1]; }
 }
 
-template <int VEC>
+// K values of every rank for channel c of the gathered [R][C][K] buffer, staged in LDS by one parallel read: part[r * K + k]
+template <int K> __device__ __forceinline__ void stage_ranks(const Args& a, int c, double* part /* [K * kMaxRanks] */) {
+    for (int i = threadIdx.x; i < K * a.R; i += blockDim.x) part[i] = a.gathered[((size_t)(i / K) * a.C + c) * K + i % K];
+    __syncthreads();
+}
+
+// the global count, mean and sum of squared deviations of channel c from the R triples, in the order r = 0 .. R-1 in fp64; the same
+// chain in every thread of every workgroup of the channel (R is wave-uniform, at most kMaxRanks)
+__device__ __forceinline__ void combine(const Args& a, int c, double* part, double& N, double& mean, double& M2) {
+    stage_ranks<3>(a, c, part);
+    double sm = 0.0;
+    N = 0.0;
+    for (int r = 0; r < a.R; ++r) { N += part[3 * r]; sm += part[3 * r] * part[3 * r + 1]; }
+    mean = sm / N;
+    M2 = 0.0;
+    for (int r = 0; r < a.R; ++r) {
+        const double d = part[3 * r + 1] - mean;
+        M2 += part[3 * r + 2] + part[3 * r] * (d * d);
+    }
+}
+
+template <int VEC, bool SYNC = false>
 __global__ __launch_bounds__(kLanes) void bn_apply_kernel(Args a) {
     const int c = blockIdx.x / a.S, s = blockIdx.x % a.S;
     long lo, hi;
     share_range(a.n, a.S, s, lo, hi);
     __shared__ double part[2 * kMaxShares];
     float mean, invstd;
-    if (a.train) {
+    if constexpr (SYNC) {
+        double N, m, M2;
+        combine(a, c, part, N, m, M2);
+        const double var = M2 / N;                               // biased; M2 is a sum of non-negative terms
+        mean = (float)m;
+        invstd = (float)(1.0 / sqrt(var + (double)a.eps));
+        if (s == 0 && threadIdx.x == 0) {
+            a.mean[c] = mean; a.invstd[c] = invstd;
+            const double mo = (double)a.momentum;
+            a.run_mean[c] = (float)((1.0 - mo) * (double)a.run_mean[c] + mo * (double)mean);
+            a.run_var[c] = (float)((1.0 - mo) * (double)a.run_var[c] + mo * (M2 / (N - 1.0)));
+        }
+    } else if (a.train) {
         double f0, f1;
         fold(a, c, part, f0, f1);
         const double n = (double)a.n, d = f0 / n;               // mean - pivot
@@ -273,18 +322,26 @@ __global__ __launch_bounds__(kLanes) void bn_bwd_reduce_kernel(Args a) {
     }
 }
 
-template <int VEC>
+template <int VEC, bool SYNC = false>
 __global__ __launch_bounds__(kLanes) void bn_bwd_apply_kernel(Args a) {
     const int c = blockIdx.x / a.S, s = blockIdx.x % a.S;
     long lo, hi;
     share_range(a.n, a.S, s, lo, hi);
     __shared__ double part[2 * kMaxShares];
     double f0, f1;
-    fold(a, c, part, f0, f1);
-    if (s == 0 && threadIdx.x == 0) { a.g_beta[c] = (float)f0; a.g_gamma[c] = (float)f1; }
+    float k1, k2;
+    if constexpr (SYNC) {   // the sums of all ranks, added in rank order; g_gamma / g_beta are the fold launch's
+        stage_ranks<2>(a, c, part);
+        f0 = 0.0; f1 = 0.0;
+        for (int r = 0; r < a.R; ++r) { f0 += part[2 * r]; f1 += part[2 * r + 1]; }
+        k1 = (float)(f0 / a.N); k2 = (float)(f1 / a.N);
+    } else {
+        fold(a, c, part, f0, f1);
+        if (s == 0 && threadIdx.x == 0) { a.g_beta[c] = (float)f0; a.g_gamma[c] = (float)f1; }
+        k1 = a.train ? (float)(f0 / (double)a.n) : 0.f; k2 = a.train ? (float)(f1 / (double)a.n) : 0.f;
+    }
     const float mean = a.mean_in[c], invstd = a.var_in[c];
     const float scale = scale_of(invstd, a.gamma[c]), beta = a.beta[c];
-    const float k1 = a.train ? (float)(f0 / (double)a.n) : 0.f, k2 = a.train ? (float)(f1 / (double)a.n) : 0.f;
     const bool relu = a.relu != 0;
     walk<VEC>(a, c, lo, hi, [&](size_t base, int v, int v1) {
         float r[kUnroll][VEC], q[kUnroll][VEC];
@@ -310,12 +367,16 @@ __global__ __launch_bounds__(kLanes) void bn_bwd_apply_kernel(Args a) {
     });
 }
 
-// g_gamma / g_beta alone (no gx wanted): the same fold, one workgroup per channel
+// g_gamma / g_beta alone (no gx wanted): the same fold, one workgroup per channel.  SYNC: also the fp64 pair that travels
+template <bool SYNC = false>
 __global__ __launch_bounds__(64) void bn_bwd_fold_kernel(Args a) {
     __shared__ double part[2 * kMaxShares];
     double f0, f1;
     fold(a, blockIdx.x, part, f0, f1);
-    if (threadIdx.x == 0) { a.g_beta[blockIdx.x] = (float)f0; a.g_gamma[blockIdx.x] = (float)f1; }
+    if (threadIdx.x == 0) {
+        a.g_beta[blockIdx.x] = (float)f0; a.g_gamma[blockIdx.x] = (float)f1;
+        if constexpr (SYNC) { a.dout[2 * blockIdx.x] = f0; a.dout[2 * blockIdx.x + 1] = f1; }
+    }
 }
 
 inline bool geometry(int B, int C, int V, Args& a) {
@@ -398,8 +459,10 @@ extern "C" int dmvs_bn_relu_backward(const float* x, const float* gy, const floa
     if (vec) bn::bn_bwd_reduce_kernel<4><<<grid, bn::kLanes, 0, st>>>(a);
     else bn::bn_bwd_reduce_kernel<1><<<grid, bn::kLanes, 0, st>>>(a);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-    if (!gx) bn::bn_bwd_fold_kernel<<<dim3((unsigned)C), 64, 0, st>>>(a);
+    if (!gx) bn::bn_bwd_fold_kernel<false><<<dim3((unsigned)C), 64, 0, st>>>(a);
     else if (vec) bn::bn_bwd_apply_kernel<4><<<grid, bn::kLanes, 0, st>>>(a);
     else bn::bn_bwd_apply_kernel<1><<<grid, bn::kLanes, 0, st>>>(a);
     DMVS_LAUNCH_CHECK();
 }
+
+#include "batchnorm_sync.h"

@@ -1400,3 +1400,103 @@ def bn_relu_backward(x: torch.Tensor, gy: torch.Tensor, gamma: torch.Tensor, bet
             f"bn{C}", "bn_relu_backward", x, (gy, gamma, beta, mean, invstd, workspace), False, "batchnorm", cost)
     _log("batchnorm")   # two dispatches: the partial sums, then fold + apply (or the fold alone)
     return gx, g_gamma, g_beta
+
+
+# ------------------------------------------------------------------------------------------ K5, synchronised statistics
+BN_MAX_RANKS = 16   # csrc/batchnorm.h kMaxRanks: ranks whose statistics one launch combines
+
+
+def _bn_gathered(what: str, t: torch.Tensor, x: torch.Tensor, C: int, K: int) -> int:
+    """A gathered [R][C][K] fp64 buffer on x's device -> R."""
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.device != x.device or t.dim() != 3 or tuple(t.shape[1:]) != (C, K):
+        raise _lib.DmvsError(f"{what}: the gathered buffer must be a contiguous float64 [R,{C},{K}] on {x.device}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    R = int(t.shape[0])
+    if not 1 <= R <= BN_MAX_RANKS:
+        raise _lib.DmvsError(f"{what}: {R} ranks; the kernels combine 1 .. {BN_MAX_RANKS}")
+    return R
+
+
+def _bn_sync_ws(what: str, x: torch.Tensor, B: int, C: int, V: int, workspace):
+    if workspace is None:
+        return bn_workspace(C, B, V, x.device)
+    if workspace.numel() < _lib.load().dmvs_bn_workspace(C, B, V):
+        raise _lib.DmvsError(f"{what}: workspace too small")
+    return workspace
+
+
+def bn_sync_moments(x: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """This rank's moments of x [B,C,...]: float64 [C,3] = (n, mean, sum of squared deviations about that mean) per channel -- what
+    travels between ranks (an all-gather along a new first axis gives ``bn_sync_forward`` its ``gathered``)."""
+    _req(x, workspace)
+    B, C, V = _bn_dims(x)
+    workspace = _bn_sync_ws("bn_sync_moments", x, B, C, V, workspace)
+    moments = torch.empty((C, 3), dtype=torch.float64, device=x.device)
+    cost = (3.0 * B * C * V, 4.0 * B * C * V, None) if timer is not None else None
+    _launch(_lib.load().dmvs_bn_sync_moments, (_ptr(x), _ptr(moments), _ptr(workspace), B, C, V),
+            f"bn{C}", "bn_sync_moments", x, (workspace,), False, "batchnorm", cost)
+    _log("batchnorm")   # two dispatches: the partial statistics, then their fold
+    return moments
+
+
+def bn_sync_forward(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor, running_var: torch.Tensor,
+                    gathered: torch.Tensor, momentum: float, eps: float, relu: bool):
+    """K5 forward on the statistics of all ranks.  ``gathered`` float64 [R,C,3]: the ``bn_sync_moments`` of every rank in rank order.
+    -> (y, mean, invstd, N): y = relu(BatchNorm(x)) under the global mean and biased variance, mean / invstd [C] (the same bits on every
+    rank), N the global count per channel (a host integer: the call reads the R counts back and synchronises the stream once).  The
+    running buffers are blended in place with the global mean and unbiased variance."""
+    _req(x, gamma, beta, running_mean, running_var)
+    B, C, V = _bn_dims(x)
+    _bn_vectors("bn_sync_forward", C, x, gamma, beta, running_mean, running_var)
+    R = _bn_gathered("bn_sync_forward", gathered, x, C, 3)
+    y = torch.empty_like(x)
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    n_total = ctypes.c_long(0)
+    cost = (5.0 * B * C * V, 4.0 * B * C * V * 2, None) if timer is not None else None
+    _launch(_lib.load().dmvs_bn_sync_forward,
+            (_ptr(x), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(gathered), _ptr(y), _ptr(mean), _ptr(invstd),
+             ctypes.byref(n_total), B, C, V, R, float(momentum), float(eps), RELU if relu else 0),
+            f"bn{C}", "bn_sync_forward", x, (gamma, beta, running_mean, running_var, gathered), False, "batchnorm", cost)
+    return y, mean, invstd, n_total.value
+
+
+def bn_sync_backward_sums(x: torch.Tensor, gy: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor,
+                          invstd: torch.Tensor, relu: bool, workspace: Optional[torch.Tensor] = None):
+    """This rank's backward sums under the global mean / invstd of ``bn_sync_forward``: -> (sums float64 [C,2] = (sum g, sum g * xhat)
+    -- what travels --, g_gamma, g_beta): the two fp32 gradients are the LOCAL sums."""
+    _req(x, gy, gamma, beta, mean, invstd, workspace)
+    if gy.shape != x.shape:
+        raise _lib.DmvsError(f"bn_sync_backward_sums: x {tuple(x.shape)} and gy {tuple(gy.shape)} must have the same shape")
+    B, C, V = _bn_dims(x)
+    _bn_vectors("bn_sync_backward_sums", C, x, gamma, beta, mean, invstd)
+    workspace = _bn_sync_ws("bn_sync_backward_sums", x, B, C, V, workspace)
+    sums = torch.empty((C, 2), dtype=torch.float64, device=x.device)
+    g_gamma = torch.empty(C, dtype=torch.float32, device=x.device)
+    g_beta = torch.empty(C, dtype=torch.float32, device=x.device)
+    cost = (7.0 * B * C * V, 4.0 * B * C * V * 2, None) if timer is not None else None
+    _launch(_lib.load().dmvs_bn_sync_backward_sums,
+            (_ptr(x), _ptr(gy), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(sums), _ptr(g_gamma), _ptr(g_beta),
+             _ptr(workspace), B, C, V, RELU if relu else 0),
+            f"bn{C}", "bn_sync_backward_sums", x, (gy, gamma, beta, mean, invstd, workspace), False, "batchnorm", cost)
+    _log("batchnorm")   # two dispatches: the partial sums, then their fold
+    return sums, g_gamma, g_beta
+
+
+def bn_sync_backward_apply(x: torch.Tensor, gy: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor,
+                           invstd: torch.Tensor, gathered: torch.Tensor, N: int, relu: bool) -> torch.Tensor:
+    """gx of this rank from the sums of all ranks.  ``gathered`` float64 [R,C,2]: the ``bn_sync_backward_sums`` of every rank in rank
+    order; ``N`` the global count ``bn_sync_forward`` returned."""
+    _req(x, gy, gamma, beta, mean, invstd)
+    if gy.shape != x.shape:
+        raise _lib.DmvsError(f"bn_sync_backward_apply: x {tuple(x.shape)} and gy {tuple(gy.shape)} must have the same shape")
+    B, C, V = _bn_dims(x)
+    _bn_vectors("bn_sync_backward_apply", C, x, gamma, beta, mean, invstd)
+    R = _bn_gathered("bn_sync_backward_apply", gathered, x, C, 2)
+    gx = torch.empty_like(x)
+    cost = (8.0 * B * C * V, 4.0 * B * C * V * 3, None) if timer is not None else None
+    _launch(_lib.load().dmvs_bn_sync_backward_apply,
+            (_ptr(x), _ptr(gy), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(gathered), _ptr(gx), B, C, V, R, int(N),
+             RELU if relu else 0),
+            f"bn{C}", "bn_sync_backward_apply", x, (gy, gamma, beta, mean, invstd, gathered), False, "batchnorm", cost)
+    return gx

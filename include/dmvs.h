@@ -667,6 +667,39 @@ int dmvs_bn_plan(int C, int B, int V);
  * Whole chunks [s * chunks / S, (s + 1) * chunks / S), the last one cut at B * V.  DMVS_EINVAL as above, and for s outside [0, S). */
 int dmvs_bn_share_range(int C, int B, int V, int s, long* lo, long* hi);
 
+/* K5, synchronised statistics: BatchNorm + ReLU in train mode over the batches of R ranks, the semantics of torch.nn.SyncBatchNorm
+ * (which the reference's train.sh switches on with --sync_bn).  The two collectives are the caller's: each entry works on device buffers
+ * and knows no process group.  Rank r holds x_r [B_r][C][V_r], n_r = B_r * V_r >= 1 values per channel; N = sum n_r >= 2.
+ * Tensors, flags (DMVS_RELU only: there is no eval form) and workspace as above; moments / sums / gathered are fp64 device buffers.
+ *
+ * dmvs_bn_sync_moments: moments[C][3] = (n_r, mean_r, M2_r), M2_r = sum (x - mean_r)^2, from partial sums around the rank's own pivot p:
+ * mean_r = p + f0 / n_r, M2_r = f1 - f0^2 / n_r with f0 = sum (x - p), f1 = sum (x - p)^2 folded in share order in fp64.  Moments travel
+ * between ranks, never raw sums: pivots differ from rank to rank.  Two launches (partial statistics; fold, C workgroups).
+ * dmvs_bn_sync_forward: gathered[R][C][3] is every rank's moments in rank order (all_gather_into_tensor of the above).  In the order
+ * r = 0 .. R-1 in fp64: N = sum n_r, mean = sum n_r mean_r / N, M2 = sum (M2_r + n_r (mean_r - mean)^2), var = M2 / N;
+ * y = relu(fmaf(x - mean, invstd * gamma, beta)), invstd = 1 / sqrt(var + eps); mean / invstd are stored; the running buffers are
+ * blended with mean and M2 / (N - 1).  Every rank reads the same buffer in the same order: mean, invstd and the running buffers are the
+ * same bits on all ranks.  *n_total (host) receives N.  The n_r are read back and checked on the host before the launch: the entry
+ * synchronises the stream once.  One launch.
+ * dmvs_bn_sync_backward_sums: g = gy * [pre > 0] on the global mean / invstd; sums[C][2] = this rank's (sum g, sum g * xhat) in fp64,
+ * g_beta / g_gamma the same two in fp32 (the LOCAL sums, as the stock module leaves them for DDP to average).  Two launches.
+ * dmvs_bn_sync_backward_apply: gathered[R][C][2] is every rank's sums in rank order; added in the order r = 0 .. R-1 in fp64;
+ * gx = gamma * invstd * (g - sum_g / N - xhat * sum_gxhat / N).  One launch.  A caller that wants no gx calls the sums entry alone.
+ * No atomics: bitwise reproducible.
+ * DMVS_EINVAL: a null pointer, C not in {8, 16, 32, 64}, B < 1, V < 1, B * V above 2^31 - 2^13, unknown flag bits, R outside [1, 16],
+ * momentum outside [0, 1], eps < 0, N < 2 (or below this rank's own B * V), a gathered n_r that is not a positive integer or differs
+ * between the channels of a rank. */
+int dmvs_bn_sync_moments(const float* x, double* moments, float* workspace, int B, int C, int V, dmvs_stream_t stream);
+int dmvs_bn_sync_forward(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                         const double* gathered, float* y, float* mean, float* invstd, long* n_total, int B, int C, int V, int R,
+                         float momentum, float eps, int flags, dmvs_stream_t stream);
+int dmvs_bn_sync_backward_sums(const float* x, const float* gy, const float* gamma, const float* beta, const float* mean,
+                               const float* invstd, double* sums, float* g_gamma, float* g_beta, float* workspace, int B, int C, int V,
+                               int flags, dmvs_stream_t stream);
+int dmvs_bn_sync_backward_apply(const float* x, const float* gy, const float* gamma, const float* beta, const float* mean,
+                                const float* invstd, const double* gathered, float* gx, int B, int C, int V, int R, long N, int flags,
+                                dmvs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

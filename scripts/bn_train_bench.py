@@ -14,6 +14,12 @@ swapped every round.  Per row and arm:
             4 bytes each -- over the time, next to the 6.3 TB/s achievable HBM rate.  Where the backward's working set (x, gy and gx:
             three tensors) is under about 256 MB the Infinity Cache may serve re-reads between passes: the column "IC" marks those.
 One JSON line; --md writes the table of profiles/bn_train.md.
+
+--sync replaces the ATen arm by the synchronised-statistics launch sequence of ``DiffSyncBatchNormReLU*`` with R = 1 and no collective:
+local moments (statistics + fold), the rank's own [1, C, 3] moments fed back as the gathered buffer, the sync apply; backward sums
+(reduce + fold), its own [1, C, 2] pair fed back, the sync backward apply -- the four ``ops.bn_sync_*`` wrappers under one autograd
+Function.  Against plain K5 it prices the two extra fold launches, the fp64 combine in the apply prologues and the read-back of the
+counts (one stream synchronisation per forward); what a collective itself costs is not in it.  --md then writes the sync table.
 """
 import argparse
 import json
@@ -72,18 +78,43 @@ def peak_mb(fn):
 
 
 def ab(arms, reps, windows):
-    """{"hip": fn, "aten": fn} -> row: every arm warmed, windows alternating with the order swapped every round."""
+    """{"hip": fn, other: fn} -> row: every arm warmed, windows alternating with the order swapped every round."""
     for fn in arms.values():
         fn()
     torch.cuda.synchronize()
     ms = {k: [] for k in arms}
+    other = next(k for k in arms if k != "hip")
     for w in range(windows):
-        for k in (("hip", "aten") if w % 2 == 0 else ("aten", "hip")):
+        for k in (("hip", other) if w % 2 == 0 else (other, "hip")):
             ms[k].append(window(arms[k], reps))
     r = {k + "_ms": spread(v) for k, v in ms.items()}
     r.update({k + "_peak_mb": peak_mb(fn) for k, fn in arms.items()})
-    r["aten_over_hip"] = r["aten_ms"]["median"] / r["hip_ms"]["median"]
+    r[other + "_over_hip"] = r[other + "_ms"]["median"] / r["hip_ms"]["median"]
     return r
+
+
+def sync_function():
+    """The sync launch sequence with R = 1 under autograd: every gathered buffer is this process's own row."""
+    from dmvsnet_amd import ops
+
+    class SyncLoop(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, weight, bias, rm, rv, momentum, eps):
+            xd = x.detach()
+            y, mean, invstd, N = ops.bn_sync_forward(xd, weight.detach(), bias.detach(), rm, rv, ops.bn_sync_moments(xd)[None], momentum,
+                                                     eps, True)
+            ctx.save_for_backward(xd, weight, bias, mean, invstd)
+            ctx.N = N
+            return y
+
+        @staticmethod
+        def backward(ctx, gy):
+            x, weight, bias, mean, invstd = ctx.saved_tensors
+            gy, w, b = gy.contiguous(), weight.detach(), bias.detach()
+            sums, g_gamma, g_beta = ops.bn_sync_backward_sums(x, gy, w, b, mean, invstd, True)
+            return ops.bn_sync_backward_apply(x, gy, w, b, mean, invstd, sums[None], ctx.N, True), g_gamma, g_beta, None, None, None, None
+
+    return SyncLoop
 
 
 def main():
@@ -92,12 +123,15 @@ def main():
     ap.add_argument("--windows", type=int, default=6)
     ap.add_argument("--rows", default="", help="comma-separated substrings: only the rows that contain one of them")
     ap.add_argument("--md", default=None, help="also write the result table (markdown) to this file")
+    ap.add_argument("--sync", action="store_true", help="second arm: the synchronised-statistics launch sequence with R = 1, not ATen")
     args = ap.parse_args()
 
     from dmvsnet_amd import DiffBatchNormReLU2d, DiffBatchNormReLU3d
     assert torch.cuda.is_available(), "the benchmark needs the MI355X"
     dev = torch.device("cuda:0")
-    out = dict(bench="bn_train", device=torch.cuda.get_device_name(0), reps=args.reps, windows=args.windows, rows={})
+    other = "sync" if args.sync else "aten"
+    sync_fn = sync_function() if args.sync else None
+    out = dict(bench="bn_train_sync" if args.sync else "bn_train", device=torch.cuda.get_device_name(0), reps=args.reps, windows=args.windows, rows={})
     want = [s for s in args.rows.split(",") if s]
     for name, C, nd, spatial in rows():
         if want and not any(s in name for s in want):
@@ -118,7 +152,11 @@ def main():
         def aten_arm():
             return torch.autograd.grad(F.relu(F.batch_norm(x, rm, rv, hip.weight, hip.bias, True, 0.1, hip.eps)), [x, hip.weight, hip.bias], gy)
 
-        gh, ga = hip_arm(), aten_arm()
+        def sync_arm():
+            return torch.autograd.grad(sync_fn.apply(x, hip.weight, hip.bias, rm, rv, 0.1, hip.eps), [x, hip.weight, hip.bias], gy)
+
+        other_arm = sync_arm if args.sync else aten_arm
+        gh, ga = hip_arm(), other_arm()
         # the two arms round the statistics differently: an element whose pre-activation lies within that rounding of the ReLU kink
         # gets the other mask, and its g_x differs by a whole gy * scale.  Such elements are counted, not averaged away.
         dx = (gh[0] - ga[0]).abs() / ga[0].abs().max()
@@ -126,18 +164,19 @@ def main():
         n_flipped = int(flipped.sum())
         agree = max([dx[~flipped].max().item()] + [((a - b).abs().max() / b.abs().max()).item() for a, b in zip(gh[1:], ga[1:])])
         del gh, ga, dx, flipped
-        r = ab({"hip": hip_arm, "aten": aten_arm}, args.reps, args.windows)
+        r = ab({"hip": hip_arm, other: other_arm}, args.reps, args.windows)
         nbytes = 4.0 * x.numel()
         r.update(C=C, shape=" x ".join(str(n) for n in spatial), tensor_mb=nbytes / 2 ** 20, gradients_rel_diff=agree, kink_flips=n_flipped,
-                 hip_gbs=PASSES * nbytes / (r["hip_ms"]["median"] * 1e-3) / 1e9, aten_gbs=PASSES * nbytes / (r["aten_ms"]["median"] * 1e-3) / 1e9)
+                 hip_gbs=PASSES * nbytes / (r["hip_ms"]["median"] * 1e-3) / 1e9)
+        r[other + "_gbs"] = PASSES * nbytes / (r[other + "_ms"]["median"] * 1e-3) / 1e9
         out["rows"][name] = r
-        print(f"# {name}: hip {r['hip_ms']['median']:.3f} ms ({r['hip_gbs']:.0f} GB/s)  aten {r['aten_ms']['median']:.3f} ms  peak "
-              f"{r['hip_peak_mb']:.0f} / {r['aten_peak_mb']:.0f} MB  gradients differ by {agree:.1e} ({n_flipped} kink flips)", file=sys.stderr, flush=True)
+        print(f"# {name}: hip {r['hip_ms']['median']:.3f} ms ({r['hip_gbs']:.0f} GB/s)  {other} {r[other + '_ms']['median']:.3f} ms  peak "
+              f"{r['hip_peak_mb']:.0f} / {r[other + '_peak_mb']:.0f} MB  gradients differ by {agree:.1e} ({n_flipped} kink flips)", file=sys.stderr, flush=True)
         del x, gy, hip
     print(json.dumps(out))
     if args.md:
         with open(args.md, "w") as f:
-            f.write(markdown(out))
+            f.write(markdown_sync(out) if args.sync else markdown(out))
 
 
 def markdown(out):
@@ -159,6 +198,24 @@ def markdown(out):
                      f"{r['hip_ms']['median']:.3f} | {r['aten_ms']['median']:.3f} | {r['aten_over_hip']:.2f} | {r['hip_gbs']:.0f} | "
                      f"{r['aten_gbs']:.0f} | {r['hip_gbs'] / HBM_GBS:.2f} | {r['hip_peak_mb']:.0f} | {r['aten_peak_mb']:.0f} | "
                      f"{r['gradients_rel_diff']:.1e} | {r['kink_flips']} |")
+    lines.append("")
+    return "\n".join(lines)
+
+
+def markdown_sync(out):
+    lines = ["## Synchronised statistics: the sync launch sequence against plain K5", "",
+             f"`scripts/bn_train_bench.py --sync` on {out['device']}, one process, arms alternating; median of {out['windows']} windows of "
+             f"{out['reps']} repetitions, batch 1, forward + backward, times in ms.  `sync`: local moments (statistics + fold), the "
+             "rank's own moments fed back as the gathered buffer (R = 1, no collective), sync apply; backward sums (reduce + fold), fed "
+             "back, sync backward apply.  `sync - hip` is the price of the two extra fold launches, the fp64 combine in the two apply "
+             "prologues and the read-back of the counts (one stream synchronisation per forward).  The collectives themselves are not "
+             "in it: their latency over RCCL between GPUs is unmeasured.", "",
+             "| blocks | C | volume | tensor MB | hip fwd+bwd | sync fwd+bwd | sync - hip | sync / hip | outputs, max rel. diff |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for name, r in out["rows"].items():
+        h, s = r["hip_ms"]["median"], r["sync_ms"]["median"]
+        lines.append(f"| {name} | {r['C']} | {r['shape']} | {r['tensor_mb']:.1f} | {h:.3f} | {s:.3f} | {s - h:.3f} | {s / h:.2f} | "
+                     f"{r['gradients_rel_diff']:.1e} |")
     lines.append("")
     return "\n".join(lines)
 

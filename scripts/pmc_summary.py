@@ -23,7 +23,8 @@ DMVS_KERNELS = ("mfma_kernel", "wino_kernel", "warp_corr", "conv_cout2", "conv_d
                 "conv_wgrad_c2_kernel", "conv_wgrad_c2_reduce_kernel",
                 "conv_wgrad_k5s2_kernel", "conv_wgrad_k5s2_reduce_kernel", "conv_dgrad_k5s2_kernel",
                 "conv_wgrad_fpn_kernel", "conv_wgrad_fpn_reduce_kernel",
-                "bn_stats_kernel", "bn_apply_kernel", "bn_bwd_reduce_kernel", "bn_bwd_apply_kernel", "bn_bwd_fold_kernel")
+                "bn_stats_kernel", "bn_apply_kernel", "bn_bwd_reduce_kernel", "bn_bwd_apply_kernel", "bn_bwd_fold_kernel",
+                "bn_moments_kernel")
 
 args = sys.argv[1:]
 log = None
