@@ -14,13 +14,15 @@ this backward returns for them is the reference's behaviour, not an omission.
 
 The forward is the product kernel (quad-planar features, direct-form coordinates); the backward recomputes the taps with the
 generic kernel's routine in the reference's op order.  The two differ by < 1e-4 px in the tap position,
-i.e. the gradient is taken at taps that differ from the forward's at the fp32 rounding level.  The source-view gradients are
-accumulated with floating-point atomics: they are equal run to run only to fp32 rounding; the reference-view gradient is
-bitwise reproducible.
+i.e. the gradient is taken at taps that differ from the forward's at the fp32 rounding level.  The reference-view gradient is
+bitwise reproducible.  The source-view gradients are accumulated with floating-point atomics by default: equal run to run only to
+fp32 rounding.  In DETERMINISTIC mode (``deterministic=True``, or ``None`` under ``torch.use_deterministic_algorithms(True)``)
+they are accumulated in fixed point instead (``ops.warp_corr_backward_det``, csrc/warp_corr_bwd_det.h): bitwise reproducible, a pure
+function of the sample's inputs -- independent of the batch around it and of which other views want a gradient.
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 from torch import nn
@@ -32,11 +34,14 @@ SUPPORTED_C = (8, 16, 32)
 
 # launches of the two backward kernels since import (tests check through them that a frozen input skips its kernel)
 launch_counts = {"bwd_ref": 0, "bwd_src_views": 0}
+# the same for backwards taken in deterministic mode (which leave ``launch_counts`` alone)
+det_launch_counts = {"bwd_ref": 0, "bwd_src_views": 0}
 
 
 class _CostAggFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, proj_matrices, depth_values, *features):
+    def forward(ctx, deterministic, proj_matrices, depth_values, *features):
+        ctx.deterministic = bool(deterministic)
         B, C, H, W = features[0].shape
         D = depth_values.shape[1]
         V = len(features)
@@ -59,29 +64,41 @@ class _CostAggFn(torch.autograd.Function):
         q4, proj12, depth = ctx.saved_tensors
         B, V = q4.shape[:2]
         C, H, W = 4 * q4.shape[2], q4.shape[3], q4.shape[4]
-        need = ctx.needs_input_grad[2:]
+        need = ctx.needs_input_grad[3:]
+        det = ctx.deterministic
         gsim = gsim.contiguous()
         grads: List = [None] * V
         if need[0]:
             grads[0] = torch.empty((B, C, H, W), dtype=torch.float32, device=q4.device)
         for v in range(1, V):
-            if need[v]:
-                grads[v] = torch.zeros((B, C, H, W), dtype=torch.float32, device=q4.device)
+            if need[v]:   # the fixed-point path writes every element; the atomics add into zeros
+                grads[v] = (torch.empty if det else torch.zeros)((B, C, H, W), dtype=torch.float32, device=q4.device)
         if any(need):
+            nact = sum(int(n) for n in need[1:])
+            counts = det_launch_counts if det else launch_counts
+            ws = None
+            if det and nact:   # one workspace for the batch: the samples run one after the other on one stream
+                ws = torch.empty((ops.warp_corr_backward_det_workspace(C, H, W, nact) // 8,), dtype=torch.int64, device=q4.device)
             for b in range(B):
-                ops.warp_corr_backward(q4[b, 0], [q4[b, v] for v in range(1, V)], proj12[b], depth[b], gsim[b],
-                                       None if grads[0] is None else grads[0][b],
-                                       [None if grads[v] is None else grads[v][b] for v in range(1, V)])
-                launch_counts["bwd_ref"] += int(need[0])
-                launch_counts["bwd_src_views"] += sum(int(n) for n in need[1:])
-        # cameras, hypotheses: the reference's grid is built under no_grad (module.py:222-243) -- no gradient exists
-        return (None, None, *grads)
+                args = (q4[b, 0], [q4[b, v] for v in range(1, V)], proj12[b], depth[b], gsim[b],
+                        None if grads[0] is None else grads[0][b], [None if grads[v] is None else grads[v][b] for v in range(1, V)])
+                if det:
+                    ops.warp_corr_backward_det(*args, workspace=ws)
+                else:
+                    ops.warp_corr_backward(*args)
+                counts["bwd_ref"] += int(need[0])
+                counts["bwd_src_views"] += nact
+        # the mode; cameras, hypotheses: the reference's grid is built under no_grad (module.py:222-243) -- no gradient exists
+        return (None, None, None, *grads)
 
 
-def cost_agg(features: Sequence[torch.Tensor], proj_matrices: torch.Tensor, depth_values: torch.Tensor) -> torch.Tensor:
+def cost_agg(features: Sequence[torch.Tensor], proj_matrices: torch.Tensor, depth_values: torch.Tensor,
+             deterministic: Optional[bool] = None) -> torch.Tensor:
     """features: V tensors [B,C,H,W] fp32 on a HIP device, reference view first; proj_matrices [B,V,2,4,4]; depth_values
     [B,D,H,W] -> similarity volume [B,2,D,H,W] (group k = mean over g of warped[2g+k] * ref[2g+k], summed over the source
-    views), differentiable with respect to the feature maps."""
+    views), differentiable with respect to the feature maps.  ``deterministic``: True / False force the mode of the backward's
+    source-view gradients (fixed-point, bitwise reproducible / fp32 atomics); None follows
+    ``torch.are_deterministic_algorithms_enabled()`` at the time of this forward.  The forward and dRef are the same either way."""
     features = list(features)
     V = len(features)
     for t in (*features, proj_matrices, depth_values):
@@ -102,20 +119,23 @@ def cost_agg(features: Sequence[torch.Tensor], proj_matrices: torch.Tensor, dept
         raise _lib.DmvsError(f"cost_agg: proj_matrices must be [B,V,2,4,4] = {(B, V, 2, 4, 4)}, got {tuple(proj_matrices.shape)}")
     if depth_values.dim() != 4 or depth_values.shape[0] != B or tuple(depth_values.shape[2:]) != (H, W):
         raise _lib.DmvsError(f"cost_agg: depth_values must be [B,D,H,W] with the features' B, H, W, got {tuple(depth_values.shape)}")
-    return _CostAggFn.apply(proj_matrices, depth_values, *features)
+    if deterministic is None:
+        deterministic = torch.are_deterministic_algorithms_enabled()
+    return _CostAggFn.apply(bool(deterministic), proj_matrices, depth_values, *features)
 
 
 class DiffCostAgg(nn.Module):
     """Drop-in for the reference's ``CostAgg`` (networks/mvsnet.py:102-153, "variance" mode) that autograd can differentiate.
     Owns no parameters; train and eval mode compute the same thing."""
 
-    def __init__(self, mode="variance", in_channels=None):
+    def __init__(self, mode="variance", in_channels=None, deterministic=None):
         super().__init__()
         assert mode in ("variance", "adaptive"), "Don't support {}!".format(mode)
         if mode == "adaptive":
             raise NotImplementedError("agg_mode='adaptive' is unreachable from the reference's scripts "
                                       "(SURVEY.md section 2 row 8) and is not built")
         self.mode = mode
+        self.deterministic = deterministic   # as cost_agg's keyword
 
     def forward(self, features, proj_matrices, depth_values, stage_idx=None):
-        return cost_agg(features, proj_matrices, depth_values)
+        return cost_agg(features, proj_matrices, depth_values, deterministic=self.deterministic)

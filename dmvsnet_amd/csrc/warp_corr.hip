@@ -694,3 +694,7 @@ extern "C" int dmvs_warp_corr_q4_f16(const void* ref_q4h, const void* const* src
 // ------------------------------------------------------------------------------------------------
 // K1b: the backward kernels (dRef gather, dSrc scatter) and dmvs_warp_corr_backward
 #include "warp_corr_bwd.h"
+
+// ------------------------------------------------------------------------------------------------
+// K1b, deterministic mode: fixed-point dSrc scatter and dmvs_warp_corr_backward_det
+#include "warp_corr_bwd_det.h"

@@ -81,7 +81,8 @@ __global__ __launch_bounds__(kBwdTX * kBwdTY) void warp_corr_bwd_ref_kernel(Warp
 // dSrc: every sample adds w_tap * (2/C) G Ref to its four taps with fp32 global atomics (return value unused: the
 // no-return form).  blockIdx.z = (active view, quad group, chunk of DCH planes).  A tap outside the image is skipped,
 // as ATen's grid_sample backward skips it; the clamped coordinates keep every address inside the gradient.  The order
-// in which the atomics of different waves arrive is not fixed: the result is reproducible to fp32 rounding only.
+// in which the atomics of different waves arrive is not fixed: the result is reproducible to fp32 rounding only
+// (warp_corr_bwd_det.h is the order-free form of this kernel).
 template <int NQ, int QPT, int DCH>
 __global__ __launch_bounds__(kBwdTX * kBwdTY) void warp_corr_bwd_src_kernel(WarpBwdArgs a, int nqg, int nch) {
     const int x = blockIdx.x * kBwdTX + threadIdx.x, y = blockIdx.y * kBwdTY + threadIdx.y;

@@ -347,6 +347,53 @@ def warp_corr_backward(ref_q4: torch.Tensor, src_q4: Sequence[torch.Tensor], pro
                                                    garr, C, D, H, W, _stream()), "dmvs_warp_corr_backward")
 
 
+def warp_corr_backward_det_workspace(C: int, H: int, W: int, nact: int) -> int:
+    """Bytes of the int64 workspace of ``warp_corr_backward_det`` for ``nact`` wanted source views."""
+    return int(_lib.load().dmvs_warp_corr_backward_det_workspace(C, H, W, nact))
+
+
+def warp_corr_backward_det(ref_q4: torch.Tensor, src_q4: Sequence[torch.Tensor], proj12: torch.Tensor, depth_dhw: torch.Tensor,
+                           gsim: torch.Tensor, gref: Optional[torch.Tensor], gsrc: Sequence[Optional[torch.Tensor]],
+                           workspace: Optional[torch.Tensor] = None, variant: int = 0) -> None:
+    """K1b in deterministic mode: as ``warp_corr_backward``, but the source gradients are accumulated in fixed point (order-free:
+    a pure function of the inputs) and every wanted gsrc[v] is WRITTEN, so it needs no zero fill.  ``workspace``: a contiguous
+    int64 HIP tensor of at least ``warp_corr_backward_det_workspace(C, H, W, nact) / 8`` elements (allocated when None; the
+    kernels clear it).  ``variant``: launch-configuration knob (0 default, 1 another decomposition, the same bits).  Not logged as
+    a launch family."""
+    src_q4, gsrc = list(src_q4), list(gsrc)
+    live = [g for g in gsrc if g is not None]
+    if depth_dhw.dim() != 3 or ref_q4.dim() != 4 or ref_q4.shape[-1] != 4:
+        raise _lib.DmvsError("warp_corr_backward_det: depth must be [D,H,W] and the features quad-planar [C/4,H,W,4]")
+    D, H, W = depth_dhw.shape
+    C = 4 * ref_q4.shape[0]
+    nsrc = len(src_q4)
+    if len(gsrc) != nsrc or proj12.dim() != 2 or tuple(proj12.shape) != (nsrc, 12) or tuple(gsim.shape) != (2, D, H, W):
+        raise _lib.DmvsError(f"warp_corr_backward_det: {nsrc} source views need {nsrc} gsrc entries, proj12 [{nsrc},12] and gsim "
+                             f"{(2, D, H, W)}; got {len(gsrc)}, {tuple(proj12.shape)}, {tuple(gsim.shape)}")
+    for s in (ref_q4, *src_q4):
+        if tuple(s.shape) != (C // 4, H, W, 4):
+            raise _lib.DmvsError(f"warp_corr_backward_det: feature map {tuple(s.shape)}, expected {(C // 4, H, W, 4)}")
+    for g in (gref, *live):
+        if g is not None and tuple(g.shape) != (C, H, W):
+            raise _lib.DmvsError(f"warp_corr_backward_det: gradient {tuple(g.shape)}, expected {(C, H, W)}")
+    _req(ref_q4, proj12, depth_dhw, gsim, gref, *src_q4, *live)
+    if gref is None and not live:
+        return
+    need = warp_corr_backward_det_workspace(C, H, W, len(live)) if live else 0
+    if live and workspace is None:
+        workspace = torch.empty((need // 8,), dtype=torch.int64, device=ref_q4.device)
+    nbytes = 0
+    if workspace is not None:
+        if not (workspace.is_cuda and workspace.dtype == torch.int64 and workspace.is_contiguous()):
+            raise _lib.DmvsError("warp_corr_backward_det: the workspace must be a contiguous int64 HIP tensor")
+        nbytes = workspace.numel() * 8
+    arr = (ctypes.c_void_p * nsrc)(*[s.data_ptr() for s in src_q4])
+    garr = (ctypes.c_void_p * nsrc)(*[None if g is None else g.data_ptr() for g in gsrc])
+    _lib.check(_lib.load().dmvs_warp_corr_backward_det(_ptr(ref_q4), arr, nsrc, _ptr(proj12), _ptr(depth_dhw), _ptr(gsim), _ptr(gref),
+                                                       garr, C, D, H, W, _ptr(workspace), nbytes, int(variant), _stream()),
+               "dmvs_warp_corr_backward_det")
+
+
 def warp_corr(ref: torch.Tensor, src: Sequence[torch.Tensor], proj12: torch.Tensor, depth_dhw: torch.Tensor,
               out: Optional[torch.Tensor] = None, accumulate: bool = False, C: Optional[int] = None,
               pix_stride: Optional[int] = None, variant: int = 0, family: str = "warp_corr",

@@ -19,6 +19,8 @@
 #ifndef DMVS_H
 #define DMVS_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -199,11 +201,35 @@ int dmvs_warp_corr_q4_f16(const void* ref_q4h, const void* const* src_q4h, int n
  *   gref_chw                  [C][H][W] planar, or NULL: the reference-gradient kernel is skipped
  *   gsrc_chw (host)           array of nsrc device pointers to [C][H][W] planar gradients that the CALLER has zeroed, or
  *                             NULL; a NULL entry skips that view; all NULL skips the source-gradient kernel
- * The source gradients depend on the arrival order of the atomics: equal run to run only to fp32 rounding.
+ * The source gradients depend on the arrival order of the atomics: equal run to run only to fp32 rounding
+ * (dmvs_warp_corr_backward_det below is the order-free form).
  * C in {8,16,32}; 1 <= nsrc <= DMVS_MAX_SRC_VIEWS; any D. */
 int dmvs_warp_corr_backward(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
                             const float* depth_dhw, const float* gsim_2dhw, float* gref_chw, float* const* gsrc_chw,
                             int C, int D, int H, int W, dmvs_stream_t stream);
+
+/* K1b, deterministic mode (additive, same version): dmvs_warp_corr_backward with the source gradients accumulated in FIXED
+ * POINT (csrc/warp_corr_bwd_det.h; docs/kernels/K1b_warp_corr_backward.md, "Deterministic mode").  Every addend
+ * t = w_tap * ((gsim * 2/C) * ref) -- the fp32 addend of the entry above -- is added as the 64-bit integer rint(t * 2^k) with an
+ * integer atomic, and a finalize kernel WRITES every element of every wanted gsrc as (float)((double)sum * 2^-k): the
+ * result is a pure function of the inputs, whatever the arrival order, the launch decomposition or the set of wanted views.
+ *   k          one per launch: min(62 - ceil(log2(D H W)), 50) - (eg + er + 2 + log2(2 / C)) with eg, er = floor(log2(max|.|))
+ *              of gsim_2dhw and of ref_q4, taken by a pre-pass on the device (no host read-back: the entry can be captured
+ *              in a graph).  A maximum of zero: every gsrc element is 0.  A maximum that is not finite (or addends that may
+ *              overflow fp32, eg + er + 2 + log2(2 / C) > 127): every element of every wanted gsrc is NaN.
+ *   gsrc_chw   as above but NOT zeroed by the caller: fully overwritten (and used as scratch before that)
+ *   gref_chw   as above: the same kernel, the same bits
+ *   workspace  dmvs_warp_corr_backward_det_workspace(C, H, W, nact) BYTES, 8-byte aligned, nact = the non-NULL gsrc entries:
+ *              the int64 sums [nact][C][H][W], cleared on the stream by the entry.  NULL, misaligned or workspace_bytes too
+ *              small with nact > 0: DMVS_EINVAL
+ *   variant    launch configuration, the same bits for every value: 0 default; 1 = planes walked in reverse, 4 planes per
+ *              chunk instead of 8, workgroups mapped in reverse (for tests of the order freedom).  Else DMVS_EINVAL.
+ * Limits as dmvs_warp_corr_backward. */
+long dmvs_warp_corr_backward_det_workspace(int C, int H, int W, int nact);
+int dmvs_warp_corr_backward_det(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
+                                const float* depth_dhw, const float* gsim_2dhw, float* gref_chw, float* const* gsrc_chw,
+                                int C, int D, int H, int W, void* workspace, size_t workspace_bytes, int variant,
+                                dmvs_stream_t stream);
 
 /* [C_total][H][W] planar slice c0..c0+C with a channel stride of chan_stride floats -> quad-planar [C/4][H][W][4]:
  * layout glue between torch feature maps (module.py:326-336: the stageK / stageK_c `split` halves are views that keep

@@ -13,6 +13,13 @@ and for the fused arm alone the two backward kernels apart (bwd_ref_ms, bwd_src_
 switched off), with the atomic payload of the source-gradient kernel (4 taps * C * 4 B per sample, all samples counted, as
 the sizing in docs/kernels/K1b_warp_corr_backward.md does) over its time; for the ATen arm grid_sample's backward alone
 (aten_grid_bwd_ms, all source views).  One JSON line; --md writes the table of profiles/costagg_train.md.
+
+--deterministic adds a third arm, cost_agg(..., deterministic=True) (K1b's fixed-point source gradients,
+csrc/warp_corr_bwd_det.h), to the same alternating windows, and for it: det_bwd_src_ms (dmvs_warp_corr_backward_det with the
+reference gradient switched off: clear + pre-pass + scatter + finalize), its workspace bytes, the added bytes of its 8-byte integer
+atomics (4 taps * C * 8 B per sample) over the scatter kernel's time, and the four steps apart -- from the device times of
+torch.profiler where it records them (det_parts_ms: clear, prepass, scatter, finalize), and always by difference
+(det_bwd_src_zero_gsim_ms: the same launch on gsim = 0, where the scatter exits at once, and det_clear_ms: a memset of the workspace).
 """
 import argparse
 import json
@@ -86,12 +93,14 @@ def main():
     ap.add_argument("--windows", type=int, default=4)
     ap.add_argument("--recipes", default=",".join(RECIPES))
     ap.add_argument("--md", default=None, help="also write the result table (markdown) to this file")
+    ap.add_argument("--deterministic", action="store_true", help="add the deterministic arm (fixed-point dSrc) beside the others")
     args = ap.parse_args()
 
     from dmvsnet_amd import cost_agg, ops, synth
     assert torch.cuda.is_available(), "the benchmark needs the MI355X"
     dev = torch.device("cuda:0")
-    out = dict(bench="costagg_train", device=torch.cuda.get_device_name(0), reps=args.reps, windows=args.windows, recipes={})
+    out = dict(bench="costagg_train", device=torch.cuda.get_device_name(0), reps=args.reps, windows=args.windows,
+               deterministic=args.deterministic, recipes={})
     for recipe in args.recipes.split(","):
         Hf, Wf, V = RECIPES[recipe]
         cams = synth.synth_cameras(Hf, Wf, V)
@@ -112,17 +121,24 @@ def main():
             def aten():
                 torch.autograd.grad(aten_cost_agg(feats, pairs, depth), feats, gsim)
 
+            def det():
+                torch.autograd.grad(cost_agg(feats, pairs, depth, deterministic=True), feats, gsim)
+
             arms = {"fused": fused, "aten": aten}
+            if args.deterministic:
+                arms["det"] = det
             for fn in arms.values():
                 fn()
             torch.cuda.synchronize()
             ms = {k: [] for k in arms}
             for w in range(args.windows):
-                for k in (("fused", "aten") if w % 2 == 0 else ("aten", "fused")):
+                for k in (list(arms) if w % 2 == 0 else list(arms)[::-1]):
                     ms[k].append(window(arms[k], args.reps))
             r = {k + "_ms": spread(v) for k, v in ms.items()}
             r.update({k + "_peak_mb": peak_mb(fn) for k, fn in arms.items()})
             r["aten_over_fused"] = r["aten_ms"]["median"] / r["fused_ms"]["median"]
+            if args.deterministic:
+                r["det_over_fused"] = r["det_ms"]["median"] / r["fused_ms"]["median"]
 
             # the fused arm's kernels apart
             with torch.no_grad():
@@ -137,9 +153,18 @@ def main():
                 for k, fn in parts.items():
                     fn()
                     r[k] = float(np.median([window(fn, args.reps) for _ in range(args.windows)]))
+                if args.deterministic:
+                    r.update(det_parts(ops, q4, proj12, depth[0], gsim[0], V, C, H, W, args))
             payload = (V - 1) * D * H * W * 4 * C * 4
             r["bwd_src_atomic_bytes"] = payload
             r["bwd_src_atomic_tb_per_s"] = payload / (r["bwd_src_ms"] * 1e-3) / 1e12
+            if args.deterministic:
+                # the scatter alone: the profiler's kernel time, else the difference to the launch whose scatter exits at once
+                scatter = (r["det_parts_ms"] or {}).get("scatter") or (r["det_bwd_src_ms"]["median"] - r["det_bwd_src_zero_gsim_ms"])
+                r["det_scatter_ms"] = scatter
+                r["det_atomic_bytes"] = 2 * payload
+                r["det_atomic_tb_per_s"] = 2 * payload / (scatter * 1e-3) / 1e12
+                r["det_src_over_atomic_src"] = r["det_bwd_src_ms"]["median"] / r["bwd_src_ms"]
             # ATen's grid_sample backward alone (all source views)
             grids = [aten_grid(pairs, v, depth) for v in range(1, V)]
             warped = [F.grid_sample(feats[v], grids[v - 1], mode="bilinear", padding_mode="zeros", align_corners=True) for v in range(1, V)]
@@ -155,13 +180,52 @@ def main():
             rows[name] = dict(C=C, D=D, H=H, W=W, **r)
             print(f"# {recipe} {name}: fused {r['fused_ms']['median']:.3f} ms  aten {r['aten_ms']['median']:.3f} ms  "
                   f"peak {r['fused_peak_mb']:.0f} / {r['aten_peak_mb']:.0f} MB", file=sys.stderr, flush=True)
-        tot = {k: sum(rw[k]["median"] for rw in rows.values()) for k in ("fused_ms", "aten_ms")}
+        tot = {k: sum(rw[k]["median"] for rw in rows.values()) for k in ("fused_ms", "aten_ms") + (("det_ms",) if args.deterministic else ())}
+        if args.deterministic:
+            tot.update({k: sum(rw[k] for rw in rows.values()) for k in ("det_scatter_ms", "det_workspace_bytes", "det_atomic_bytes")})
+            tot["det_bwd_src_ms"] = sum(rw["det_bwd_src_ms"]["median"] for rw in rows.values())
         tot.update({k: sum(rw[k] for rw in rows.values()) for k in ("bwd_src_ms", "bwd_ref_ms", "fwd_ms", "aten_grid_bwd_ms", "bwd_src_atomic_bytes")})
         out["recipes"][recipe] = dict(views=V, passes=rows, per_sample=tot)
     print(json.dumps(out))
     if args.md:
         with open(args.md, "w") as f:
             f.write(markdown(out))
+
+
+def det_parts(ops, q4, proj12, depth, gsim, V, C, H, W, args):
+    """The deterministic source-gradient launch alone and its steps apart (see the module docstring)."""
+    dev = depth.device
+    none = [None] * (V - 1)
+    gsrc = [torch.empty((C, H, W), device=dev) for _ in range(V - 1)]
+    nbytes = ops.warp_corr_backward_det_workspace(C, H, W, V - 1)
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+    zero = torch.zeros_like(gsim)
+    run = lambda g=gsim: ops.warp_corr_backward_det(q4[0], q4[1:], proj12, depth, g, None, gsrc, workspace=ws)   # noqa: E731
+    run()
+    r = dict(det_workspace_bytes=nbytes, det_bwd_src_ms=spread([window(run, args.reps) for _ in range(args.windows)]))
+    r["det_bwd_src_zero_gsim_ms"] = float(np.median([window(lambda: run(zero), args.reps) for _ in range(args.windows)]))
+    r["det_clear_ms"] = float(np.median([window(ws.zero_, args.reps) for _ in range(args.windows)]))
+    parts = None
+    try:   # device times per kernel; None where the profiler records no device activity
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(args.reps):
+                run()
+            torch.cuda.synchronize()
+        keys = {"prepass": "det_absmax", "scatter": "det_src", "finalize": "det_finalize", "clear": "emset"}
+        acc = {k: 0.0 for k in keys}
+        for ev in prof.key_averages():
+            t = getattr(ev, "device_time_total", None)
+            t = getattr(ev, "cuda_time_total", 0.0) if t is None else t
+            for k, pat in keys.items():
+                if pat in ev.key or (k == "clear" and "fillBuffer" in ev.key):
+                    acc[k] += t / 1e3 / args.reps
+        parts = acc if acc["scatter"] > 0 else None
+    except Exception as e:   # the break-out is optional; the arm's times above are not
+        print(f"# torch.profiler break-out not available: {e!r}", file=sys.stderr)
+    r["det_parts_ms"] = parts
+    del gsrc, ws
+    return r
 
 
 def markdown(out):
@@ -177,6 +241,26 @@ def markdown(out):
             lines.append(f"| {name} | {p['C']} | {p['D']} | {p['H']} x {p['W']} | {p['fused_ms']['median']:.3f} | {p['aten_ms']['median']:.3f} | "
                          f"{p['aten_over_fused']:.2f} | {p['fwd_ms']:.3f} | {p['bwd_ref_ms']:.3f} | {p['bwd_src_ms']:.3f} | {p['aten_grid_bwd_ms']:.3f} | "
                          f"{p['bwd_src_atomic_tb_per_s']:.2f} | {p['fused_peak_mb']:.0f} | {p['aten_peak_mb']:.0f} |")
+        if out.get("deterministic"):
+            lines += ["", "Deterministic mode (`cost_agg(..., deterministic=True)`: fixed-point dSrc) against the atomic arm, same windows; min / "
+                          "median / max over the windows:", "",
+                      "| pass | fused fwd+bwd | deterministic fwd+bwd | det / fused | dSrc atomic | dSrc deterministic | det / atomic | clear | pre-pass | "
+                      "scatter | finalize | scatter 8-byte atomics TB/s | workspace MB |",
+                      "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+            sp = lambda x: f"{x['min']:.3f} / {x['median']:.3f} / {x['max']:.3f}"   # noqa: E731
+            for name, p in r["passes"].items():
+                parts = p["det_parts_ms"]
+                cells = [f"{parts[k]:.3f}" for k in ("clear", "prepass", "scatter", "finalize")] if parts else \
+                        [f"{p['det_clear_ms']:.3f} (memset alone)", "n/a", f"{p['det_scatter_ms']:.3f} (by difference)", "n/a"]
+                lines.append(f"| {name} | {sp(p['fused_ms'])} | {sp(p['det_ms'])} | {p['det_over_fused']:.2f} | {p['bwd_src_ms']:.3f} | "
+                             f"{sp(p['det_bwd_src_ms'])} | {p['det_src_over_atomic_src']:.2f} | {' | '.join(cells)} | "
+                             f"{p['det_atomic_tb_per_s']:.2f} | {p['det_workspace_bytes'] / 2 ** 20:.1f} |")
+            t = r["per_sample"]
+            lines += ["", f"Per sample: deterministic {t['det_ms']:.2f} ms against fused {t['fused_ms']:.2f} ms ({t['det_ms'] / t['fused_ms']:.2f}x); "
+                          f"deterministic dSrc launches {t['det_bwd_src_ms']:.2f} ms against {t['bwd_src_ms']:.2f} ms atomic "
+                          f"({t['det_bwd_src_ms'] / t['bwd_src_ms']:.2f}x); scatter kernels {t['det_scatter_ms']:.2f} ms for "
+                          f"{t['det_atomic_bytes'] / 1e9:.2f} GB of 8-byte integer atomics "
+                          f"({t['det_atomic_bytes'] / 1e9 / t['det_scatter_ms']:.2f} TB/s)."]
         t = r["per_sample"]
         lines += ["", f"Per sample: fused {t['fused_ms']:.2f} ms, ATen {t['aten_ms']:.2f} ms ({t['aten_ms'] / t['fused_ms']:.2f}x); "
                       f"dSrc kernels {t['bwd_src_ms']:.2f} ms for {t['bwd_src_atomic_bytes'] / 1e9:.2f} GB of atomic payload, "
