@@ -17,8 +17,9 @@ generic kernel's routine in the reference's op order.  The two differ by < 1e-4 
 i.e. the gradient is taken at taps that differ from the forward's at the fp32 rounding level.  The reference-view gradient is
 bitwise reproducible.  The source-view gradients are accumulated with floating-point atomics by default: equal run to run only to
 fp32 rounding.  In DETERMINISTIC mode (``deterministic=True``, or ``None`` under ``torch.use_deterministic_algorithms(True)``)
-they are accumulated in fixed point instead (``ops.warp_corr_backward_det``, csrc/warp_corr_bwd_det.h): bitwise reproducible, a pure
-function of the sample's inputs -- independent of the batch around it and of which other views want a gradient.
+they are accumulated in fixed point instead (``ops.warp_corr_backward_det``: the same scatter kernel on csrc/warp_corr_bwd_det.h's
+``FixedSink``): bitwise reproducible, a pure function of the sample's inputs -- independent of the batch around it and of which
+other views want a gradient.
 """
 from __future__ import annotations
 
@@ -76,16 +77,15 @@ class _CostAggFn(torch.autograd.Function):
         if any(need):
             nact = sum(int(n) for n in need[1:])
             counts = det_launch_counts if det else launch_counts
-            ws = None
-            if det and nact:   # one workspace for the batch: the samples run one after the other on one stream
-                ws = torch.empty((ops.warp_corr_backward_det_workspace(C, H, W, nact) // 8,), dtype=torch.int64, device=q4.device)
+            run, mode = ops.warp_corr_backward, {}
+            if det:
+                run = ops.warp_corr_backward_det
+                if nact:   # one workspace for the batch: the samples run one after the other on one stream
+                    nbytes = ops.warp_corr_backward_det_workspace(C, H, W, nact)
+                    mode = {"workspace": torch.empty((nbytes // 8,), dtype=torch.int64, device=q4.device)}
             for b in range(B):
-                args = (q4[b, 0], [q4[b, v] for v in range(1, V)], proj12[b], depth[b], gsim[b],
-                        None if grads[0] is None else grads[0][b], [None if grads[v] is None else grads[v][b] for v in range(1, V)])
-                if det:
-                    ops.warp_corr_backward_det(*args, workspace=ws)
-                else:
-                    ops.warp_corr_backward(*args)
+                run(q4[b, 0], [q4[b, v] for v in range(1, V)], proj12[b], depth[b], gsim[b],
+                    None if grads[0] is None else grads[0][b], [None if grads[v] is None else grads[v][b] for v in range(1, V)], **mode)
                 counts["bwd_ref"] += int(need[0])
                 counts["bwd_src_views"] += nact
         # the mode; cameras, hypotheses: the reference's grid is built under no_grad (module.py:222-243) -- no gradient exists

@@ -38,6 +38,15 @@ struct WarpArgs {
     int nsrc, pix_stride, D, H, W, accumulate;
 };
 
+// An entry's nsrc view pointers into a kernel-argument array (the rest null); false when one of them is null.
+template <class T>
+static bool copy_view_ptrs(const float** dst, const T* const* src, int nsrc) {
+    for (int v = 0; v < DMVS_MAX_SRC_VIEWS; ++v) dst[v] = v < nsrc ? reinterpret_cast<const float*>(src[v]) : nullptr;
+    for (int v = 0; v < nsrc; ++v)
+        if (!dst[v]) return false;
+    return true;
+}
+
 // hypothesis plane d at pixel `pix`: from the materialised volume, or base + d * step (mul and add rounded
 // separately, like the reference's `lo + d * step`); the affine form drops the D*H*W read
 __device__ __forceinline__ float hyp_plane(const WarpArgs& a, int d, size_t plane, size_t pix, float step) {
@@ -622,9 +631,7 @@ static int warp_corr_entry(const float* ref_hwc, const float* const* src_hwc, in
     if (pix_stride < C || (pix_stride & 3)) return DMVS_EINVAL;
     WarpArgs a;
     a.ref = ref_hwc;
-    for (int v = 0; v < DMVS_MAX_SRC_VIEWS; ++v) a.src[v] = v < nsrc ? src_hwc[v] : nullptr;
-    for (int v = 0; v < nsrc; ++v)
-        if (!a.src[v]) return DMVS_EINVAL;
+    if (!copy_view_ptrs(a.src, src_hwc, nsrc)) return DMVS_EINVAL;
     a.proj = proj12; a.depth = depth_dhw; a.base = base_hw; a.step = step; a.sim = sim_2dhw;
     a.nsrc = nsrc; a.pix_stride = pix_stride; a.D = D; a.H = H; a.W = W; a.accumulate = accumulate;
     hipStream_t st = (hipStream_t)stream;
@@ -662,9 +669,7 @@ static int warp_corr_q4_entry(const void* ref_q4, const void* const* src_q4, int
     if (f16 && (W & 1)) return DMVS_EUNSUPPORTED;                  // fp16 windows are staged in pixel pairs
     WarpArgs a;
     a.ref = reinterpret_cast<const float*>(ref_q4);
-    for (int v = 0; v < DMVS_MAX_SRC_VIEWS; ++v) a.src[v] = v < nsrc ? reinterpret_cast<const float*>(src_q4[v]) : nullptr;
-    for (int v = 0; v < nsrc; ++v)
-        if (!a.src[v]) return DMVS_EINVAL;
+    if (!copy_view_ptrs(a.src, src_q4, nsrc)) return DMVS_EINVAL;
     a.proj = proj12; a.depth = depth_dhw; a.base = depth_dhw ? nullptr : base_hw; a.step = depth_dhw ? nullptr : step;
     a.sim = sim_2dhw;
     a.nsrc = nsrc; a.pix_stride = 4; a.D = D; a.H = H; a.W = W; a.accumulate = accumulate;
@@ -692,9 +697,6 @@ extern "C" int dmvs_warp_corr_q4_f16(const void* ref_q4h, const void* const* src
 }
 
 // ------------------------------------------------------------------------------------------------
-// K1b: the backward kernels (dRef gather, dSrc scatter) and dmvs_warp_corr_backward
+// K1b: the backward kernels (dRef gather, dSrc scatter), dmvs_warp_corr_backward and, through warp_corr_bwd_det.h, the
+// deterministic mode dmvs_warp_corr_backward_det
 #include "warp_corr_bwd.h"
-
-// ------------------------------------------------------------------------------------------------
-// K1b, deterministic mode: fixed-point dSrc scatter and dmvs_warp_corr_backward_det
-#include "warp_corr_bwd_det.h"

@@ -78,18 +78,21 @@ __global__ __launch_bounds__(kBwdTX * kBwdTY) void warp_corr_bwd_ref_kernel(Warp
     }
 }
 
-// dSrc: every sample adds w_tap * (2/C) G Ref to its four taps with fp32 global atomics (return value unused: the
-// no-return form).  blockIdx.z = (active view, quad group, chunk of DCH planes).  A tap outside the image is skipped,
-// as ATen's grid_sample backward skips it; the clamped coordinates keep every address inside the gradient.  The order
-// in which the atomics of different waves arrive is not fixed: the result is reproducible to fp32 rounding only
-// (warp_corr_bwd_det.h is the order-free form of this kernel).
-template <int NQ, int QPT, int DCH>
-__global__ __launch_bounds__(kBwdTX * kBwdTY) void warp_corr_bwd_src_kernel(WarpBwdArgs a, int nqg, int nch) {
+// dSrc: every sample adds t = w_tap * (2/C) G Ref to its four taps through a sink policy, which says whether the thread has
+// anything to do, where active view i's destination starts and how one fp32 addend joins it.  The addend is formed HERE, once,
+// from two fp32 products (no FMA): both sinks accumulate the same numbers.  blockIdx.z = (active view, quad group, chunk of
+// DCH planes).  A tap outside the image is skipped, as ATen's grid_sample backward skips it; the clamped coordinates keep every
+// address inside the destination.  REV: planes of a chunk walked in reverse and blockIdx.z mapped in reverse (a different
+// decomposition of the same addends, for the order-free sink's tests).
+template <int NQ, int QPT, int DCH, bool REV, class Sink>
+__global__ __launch_bounds__(kBwdTX * kBwdTY) void warp_corr_bwd_src_kernel(WarpBwdArgs a, int nqg, int nch, Sink sink) {
     const int x = blockIdx.x * kBwdTX + threadIdx.x, y = blockIdx.y * kBwdTY + threadIdx.y;
-    const int z = blockIdx.z;
+    const int z = REV ? (int)(gridDim.z - 1 - blockIdx.z) : (int)blockIdx.z;
     const int chunk = z % nch, qg = (z / nch) % nqg, i = z / (nch * nqg);
     const int W = a.W, H = a.H;
     if (x >= W || y >= H) return;
+    const typename Sink::Scale sc = sink.scale();
+    if (Sink::idle(sc)) return;
     const int v = a.view[i], q0 = qg * QPT;
     const size_t plane = (size_t)H * W, pix = (size_t)y * W + x;
     const float fx = (float)x, fy = (float)y;
@@ -100,35 +103,51 @@ __global__ __launch_bounds__(kBwdTX * kBwdTY) void warp_corr_bwd_src_kernel(Warp
     float4_t r[QPT];
 #pragma unroll
     for (int q = 0; q < QPT; ++q) r[q] = reinterpret_cast<const float4_t*>(a.ref)[(size_t)(q0 + q) * plane + pix];
-    float* const Gs = a.gsrc[i] + (size_t)q0 * 4 * plane;
-    const int dend = min((chunk + 1) * DCH, a.D);
-    for (int d = chunk * DCH; d < dend; ++d) {
+    auto* const Gs = sink.dest(a, i, (size_t)(NQ * 4) * plane) + (size_t)q0 * 4 * plane;
+    const int dbeg = chunk * DCH, dend = min((chunk + 1) * DCH, a.D);
+    for (int s = dbeg; s < dend; ++s) {
+        const int d = REV ? dbeg + dend - 1 - s : s;
         const float depth = a.depth[(size_t)d * plane + pix];
         const float g0 = a.gsim[(size_t)d * plane + pix] * inv, g1 = a.gsim[(size_t)(a.D + d) * plane + pix] * inv;
         const RefTaps t = ref_order_taps(P, fx, fy, depth, wm1, hm1, half_w, half_h);
         const bool in00 = t.x0in && t.y0in, in01 = t.x1in && t.y0in, in10 = t.x0in && t.y1in, in11 = t.x1in && t.y1in;
-        float* const p00 = Gs + t.y0 * W + t.x0;
-        float* const p01 = Gs + t.y0 * W + t.x1;
-        float* const p10 = Gs + t.y1 * W + t.x0;
-        float* const p11 = Gs + t.y1 * W + t.x1;
+        auto* const p00 = Gs + t.y0 * W + t.x0;
+        auto* const p01 = Gs + t.y0 * W + t.x1;
+        auto* const p10 = Gs + t.y1 * W + t.x0;
+        auto* const p11 = Gs + t.y1 * W + t.x1;
 #pragma unroll
         for (int q = 0; q < QPT; ++q) {
             const float gw[4] = {g0 * r[q].x, g1 * r[q].y, g0 * r[q].z, g1 * r[q].w};   // dL/dwarped of the quad
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const size_t c = (size_t)(q * 4 + j) * plane;
-                if (in00) atomicAdd(p00 + c, t.w00 * gw[j]);
-                if (in01) atomicAdd(p01 + c, t.w01 * gw[j]);
-                if (in10) atomicAdd(p10 + c, t.w10 * gw[j]);
-                if (in11) atomicAdd(p11 + c, t.w11 * gw[j]);
+                if (in00) Sink::add(p00 + c, t.w00 * gw[j], sc);
+                if (in01) Sink::add(p01 + c, t.w01 * gw[j], sc);
+                if (in10) Sink::add(p10 + c, t.w10 * gw[j], sc);
+                if (in11) Sink::add(p11 + c, t.w11 * gw[j], sc);
             }
         }
     }
 }
 
+// The default sink: fp32 global atomics (return value unused: the no-return form) into the caller's zero-initialised gsrc.  The
+// order in which the atomics of different waves arrive is not fixed: the result is reproducible to fp32 rounding only
+// (FixedSink, warp_corr_bwd_det.h, is the order-free one).
+struct AtomicSink {
+    struct Scale {};
+    __device__ __forceinline__ Scale scale() const { return {}; }
+    __device__ __forceinline__ static bool idle(Scale) { return false; }
+    __device__ __forceinline__ float* dest(const WarpBwdArgs& a, int i, size_t) const { return a.gsrc[i]; }
+    __device__ __forceinline__ static void add(float* p, float t, Scale) { atomicAdd(p, t); }
+};
+
+// the deterministic mode's scale, pre-pass, sink and finalize; needs WarpBwdArgs, needed by the launcher
+#include "warp_corr_bwd_det.h"
+
+// ws: null for the default mode, else the deterministic mode's workspace (variant: its decomposition, 0 or 1)
 template <int NQ>
-static int launch_warp_bwd(const WarpBwdArgs& a, hipStream_t st) {
-    constexpr int QPT = 2, DCH = 8;
+static int launch_warp_bwd(const WarpBwdArgs& a, long long* ws, int variant, hipStream_t st) {
+    constexpr int QPT = 2, C = NQ * 4;
     const dim3 block(kBwdTX, kBwdTY);
     const int gx = ceil_div(a.W, kBwdTX), gy = ceil_div(a.H, kBwdTY), nqg = NQ / QPT;
     if (a.gref) {
@@ -137,34 +156,74 @@ static int launch_warp_bwd(const WarpBwdArgs& a, hipStream_t st) {
         if (e != hipSuccess) return (int)e;
     }
     if (a.nact > 0) {
-        const int nch = ceil_div(a.D, DCH);
+        const int nch = ceil_div(a.D, variant ? 4 : 8);
         if ((long)a.nact * nqg * nch > 65535) return DMVS_EUNSUPPORTED;
-        warp_corr_bwd_src_kernel<NQ, QPT, DCH><<<dim3(gx, gy, a.nact * nqg * nch), block, 0, st>>>(a, nqg, nch);
+        const dim3 grid(gx, gy, a.nact * nqg * nch);
+        if (!ws) {
+            warp_corr_bwd_src_kernel<NQ, QPT, 8, false><<<grid, block, 0, st>>>(a, nqg, nch, AtomicSink{});
+        } else {
+            const size_t plane = (size_t)a.H * a.W, per_view = (size_t)C * plane, ng = 2 * (size_t)a.D * plane;
+            const int kcap = std::min(62 - det_ceil_log2((unsigned long long)a.D * plane), 50);
+            const int lc = C == 8 ? -2 : C == 16 ? -3 : -4;
+            float* const mx = a.gsrc[0];   // scratch until the last launch below
+            hipError_t e = hipMemsetAsync(mx, 0, 2 * sizeof(unsigned), st);
+            if (e == hipSuccess) e = hipMemsetAsync(ws, 0, (size_t)a.nact * per_view * sizeof(long long), st);
+            if (e != hipSuccess) return (int)e;
+            const unsigned nb = (unsigned)std::min((size_t)256, (std::max(ng, per_view) + 2047) / 2048);
+            warp_corr_det_absmax_kernel<<<dim3(nb, 2), 256, 0, st>>>(a.gsim, ng, a.ref, per_view, reinterpret_cast<unsigned*>(mx));
+            const FixedSink sink{ws, mx, kcap, lc};
+            if (variant) warp_corr_bwd_src_kernel<NQ, QPT, 4, true><<<grid, block, 0, st>>>(a, nqg, nch, sink);
+            else warp_corr_bwd_src_kernel<NQ, QPT, 8, false><<<grid, block, 0, st>>>(a, nqg, nch, sink);
+            const unsigned fb = (unsigned)((per_view + 255) / 256);   // < 2^21: per_view < 2^29
+            warp_corr_det_finalize_kernel<<<dim3(fb, a.nact), 256, 0, st>>>(a, ws, per_view, 2, per_view, mx, kcap, lc);
+            warp_corr_det_finalize_kernel<<<dim3(1, 1), 256, 0, st>>>(a, ws, per_view, 0, 2, mx, kcap, lc);
+        }
     }
     DMVS_LAUNCH_CHECK();
+}
+
+// Both public entries.  det: the deterministic mode, which needs an 8-byte aligned workspace of
+// dmvs_warp_corr_backward_det_workspace() bytes once a source gradient is wanted, and a variant of 0 or 1.
+static int warp_corr_bwd_entry(bool det, const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
+                               const float* depth_dhw, const float* gsim_2dhw, float* gref_chw, float* const* gsrc_chw, int C,
+                               int D, int H, int W, void* workspace, size_t workspace_bytes, int variant, dmvs_stream_t stream) {
+    if (!ref_q4 || !src_q4 || !proj12 || !depth_dhw || !gsim_2dhw) return DMVS_EINVAL;
+    if (nsrc < 1 || nsrc > DMVS_MAX_SRC_VIEWS || D < 1 || H < 1 || W < 1) return DMVS_EINVAL;
+    if (det && variant != 0 && variant != 1) return DMVS_EINVAL;
+    if (C != 8 && C != 16 && C != 32) return DMVS_EUNSUPPORTED;
+    if ((long)H * W * C >= (1L << 29)) return DMVS_EUNSUPPORTED;   // 32-bit tap offsets
+    WarpBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ref = ref_q4;
+    if (!copy_view_ptrs(a.src, src_q4, nsrc)) return DMVS_EINVAL;
+    for (int v = 0; v < nsrc; ++v)   // compaction: views whose gradient is not wanted are left out
+        if (gsrc_chw && gsrc_chw[v]) { a.gsrc[a.nact] = gsrc_chw[v]; a.view[a.nact] = v; ++a.nact; }
+    if (det && a.nact > 0) {
+        if (!workspace || ((uintptr_t)workspace & 7)) return DMVS_EINVAL;
+        if (workspace_bytes < (size_t)dmvs_warp_corr_backward_det_workspace(C, H, W, a.nact)) return DMVS_EINVAL;
+    }
+    a.proj = proj12; a.depth = depth_dhw; a.gsim = gsim_2dhw; a.gref = gref_chw;
+    a.nsrc = nsrc; a.D = D; a.H = H; a.W = W;
+    hipStream_t st = (hipStream_t)stream;
+    long long* ws = det && a.nact > 0 ? static_cast<long long*>(workspace) : nullptr;
+    switch (C) {
+        case 8: return launch_warp_bwd<2>(a, ws, variant, st);
+        case 16: return launch_warp_bwd<4>(a, ws, variant, st);
+        default: return launch_warp_bwd<8>(a, ws, variant, st);
+    }
 }
 
 extern "C" int dmvs_warp_corr_backward(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
                                        const float* depth_dhw, const float* gsim_2dhw, float* gref_chw,
                                        float* const* gsrc_chw, int C, int D, int H, int W, dmvs_stream_t stream) {
-    if (!ref_q4 || !src_q4 || !proj12 || !depth_dhw || !gsim_2dhw) return DMVS_EINVAL;
-    if (nsrc < 1 || nsrc > DMVS_MAX_SRC_VIEWS || D < 1 || H < 1 || W < 1) return DMVS_EINVAL;
-    if ((long)H * W * C >= (1L << 29)) return DMVS_EUNSUPPORTED;   // 32-bit tap offsets
-    WarpBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.ref = ref_q4;
-    for (int v = 0; v < nsrc; ++v) {
-        if (!src_q4[v]) return DMVS_EINVAL;
-        a.src[v] = src_q4[v];
-        if (gsrc_chw && gsrc_chw[v]) { a.gsrc[a.nact] = gsrc_chw[v]; a.view[a.nact] = v; ++a.nact; }
-    }
-    a.proj = proj12; a.depth = depth_dhw; a.gsim = gsim_2dhw; a.gref = gref_chw;
-    a.nsrc = nsrc; a.D = D; a.H = H; a.W = W;
-    hipStream_t st = (hipStream_t)stream;
-    switch (C) {
-        case 8: return launch_warp_bwd<2>(a, st);
-        case 16: return launch_warp_bwd<4>(a, st);
-        case 32: return launch_warp_bwd<8>(a, st);
-        default: return DMVS_EUNSUPPORTED;
-    }
+    return warp_corr_bwd_entry(false, ref_q4, src_q4, nsrc, proj12, depth_dhw, gsim_2dhw, gref_chw, gsrc_chw, C, D, H, W, nullptr,
+                               0, 0, stream);
+}
+
+extern "C" int dmvs_warp_corr_backward_det(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
+                                           const float* depth_dhw, const float* gsim_2dhw, float* gref_chw,
+                                           float* const* gsrc_chw, int C, int D, int H, int W, void* workspace,
+                                           size_t workspace_bytes, int variant, dmvs_stream_t stream) {
+    return warp_corr_bwd_entry(true, ref_q4, src_q4, nsrc, proj12, depth_dhw, gsim_2dhw, gref_chw, gsrc_chw, C, D, H, W, workspace,
+                               workspace_bytes, variant, stream);
 }

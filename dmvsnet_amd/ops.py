@@ -327,24 +327,47 @@ def nchw_to_q4(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     return dst
 
 
+def _warp_corr_backward(what: str, ref_q4, src_q4, proj12, depth_dhw, gsim, gref, gsrc, workspace, variant: int, det: bool) -> None:
+    """Both modes of K1b: validation (errors name the public function ``what``), the two pointer arrays and the call."""
+    src_q4, gsrc = list(src_q4), list(gsrc)
+    live = [g for g in gsrc if g is not None]
+    if depth_dhw.dim() != 3 or ref_q4.dim() != 4 or ref_q4.shape[-1] != 4:
+        raise _lib.DmvsError(f"{what}: depth must be [D,H,W] and the features quad-planar [C/4,H,W,4]")
+    D, H, W = depth_dhw.shape
+    C = 4 * ref_q4.shape[0]
+    nsrc = len(src_q4)
+    if len(gsrc) != nsrc or proj12.dim() != 2 or tuple(proj12.shape) != (nsrc, 12) or tuple(gsim.shape) != (2, D, H, W):
+        raise _lib.DmvsError(f"{what}: {nsrc} source views need {nsrc} gsrc entries, proj12 [{nsrc},12] and gsim "
+                             f"{(2, D, H, W)}; got {len(gsrc)}, {tuple(proj12.shape)}, {tuple(gsim.shape)}")
+    for s in (ref_q4, *src_q4):
+        if tuple(s.shape) != (C // 4, H, W, 4):
+            raise _lib.DmvsError(f"{what}: feature map {tuple(s.shape)}, expected {(C // 4, H, W, 4)}")
+    for g in (gref, *live):
+        if g is not None and tuple(g.shape) != (C, H, W):
+            raise _lib.DmvsError(f"{what}: gradient {tuple(g.shape)}, expected {(C, H, W)}")
+    _req(ref_q4, proj12, depth_dhw, gsim, gref, *src_q4, *live)
+    if gref is None and not live:
+        return
+    args = [_ptr(ref_q4), (ctypes.c_void_p * nsrc)(*[s.data_ptr() for s in src_q4]), nsrc, _ptr(proj12), _ptr(depth_dhw), _ptr(gsim),
+            _ptr(gref), (ctypes.c_void_p * nsrc)(*[None if g is None else g.data_ptr() for g in gsrc]), C, D, H, W]
+    if det:
+        if live and workspace is None:
+            need = warp_corr_backward_det_workspace(C, H, W, len(live))
+            workspace = torch.empty((need // 8,), dtype=torch.int64, device=ref_q4.device)
+        nbytes = 0
+        if workspace is not None:
+            if not (workspace.is_cuda and workspace.dtype == torch.int64 and workspace.is_contiguous()):
+                raise _lib.DmvsError(f"{what}: the workspace must be a contiguous int64 HIP tensor")
+            nbytes = workspace.numel() * 8
+        args += [_ptr(workspace), nbytes, int(variant)]
+    _lib.check(getattr(_lib.load(), "dmvs_" + what)(*args, _stream()), "dmvs_" + what)
+
+
 def warp_corr_backward(ref_q4: torch.Tensor, src_q4: Sequence[torch.Tensor], proj12: torch.Tensor, depth_dhw: torch.Tensor,
                        gsim: torch.Tensor, gref: Optional[torch.Tensor], gsrc: Sequence[Optional[torch.Tensor]]) -> None:
     """K1b.  Quad-planar features, gsim [2,D,H,W]; writes gref [C,H,W] (or None: skipped) and ADDS into the gsrc[v] [C,H,W]
     (zero-initialised by the caller; None: that view is skipped).  Not logged as a launch family."""
-    live = [g for g in gsrc if g is not None]
-    _req(ref_q4, proj12, depth_dhw, gsim, gref, *src_q4, *live)
-    D, H, W = depth_dhw.shape
-    C = 4 * ref_q4.shape[0]
-    nsrc = len(src_q4)
-    assert len(gsrc) == nsrc and proj12.shape[0] == nsrc and tuple(gsim.shape) == (2, D, H, W)
-    for g in (gref, *live):
-        assert g is None or tuple(g.shape) == (C, H, W), (tuple(g.shape), (C, H, W))
-    if gref is None and not live:
-        return
-    arr = (ctypes.c_void_p * nsrc)(*[s.data_ptr() for s in src_q4])
-    garr = (ctypes.c_void_p * nsrc)(*[None if g is None else g.data_ptr() for g in gsrc])
-    _lib.check(_lib.load().dmvs_warp_corr_backward(_ptr(ref_q4), arr, nsrc, _ptr(proj12), _ptr(depth_dhw), _ptr(gsim), _ptr(gref),
-                                                   garr, C, D, H, W, _stream()), "dmvs_warp_corr_backward")
+    _warp_corr_backward("warp_corr_backward", ref_q4, src_q4, proj12, depth_dhw, gsim, gref, gsrc, None, 0, False)
 
 
 def warp_corr_backward_det_workspace(C: int, H: int, W: int, nact: int) -> int:
@@ -360,38 +383,7 @@ def warp_corr_backward_det(ref_q4: torch.Tensor, src_q4: Sequence[torch.Tensor],
     int64 HIP tensor of at least ``warp_corr_backward_det_workspace(C, H, W, nact) / 8`` elements (allocated when None; the
     kernels clear it).  ``variant``: launch-configuration knob (0 default, 1 another decomposition, the same bits).  Not logged as
     a launch family."""
-    src_q4, gsrc = list(src_q4), list(gsrc)
-    live = [g for g in gsrc if g is not None]
-    if depth_dhw.dim() != 3 or ref_q4.dim() != 4 or ref_q4.shape[-1] != 4:
-        raise _lib.DmvsError("warp_corr_backward_det: depth must be [D,H,W] and the features quad-planar [C/4,H,W,4]")
-    D, H, W = depth_dhw.shape
-    C = 4 * ref_q4.shape[0]
-    nsrc = len(src_q4)
-    if len(gsrc) != nsrc or proj12.dim() != 2 or tuple(proj12.shape) != (nsrc, 12) or tuple(gsim.shape) != (2, D, H, W):
-        raise _lib.DmvsError(f"warp_corr_backward_det: {nsrc} source views need {nsrc} gsrc entries, proj12 [{nsrc},12] and gsim "
-                             f"{(2, D, H, W)}; got {len(gsrc)}, {tuple(proj12.shape)}, {tuple(gsim.shape)}")
-    for s in (ref_q4, *src_q4):
-        if tuple(s.shape) != (C // 4, H, W, 4):
-            raise _lib.DmvsError(f"warp_corr_backward_det: feature map {tuple(s.shape)}, expected {(C // 4, H, W, 4)}")
-    for g in (gref, *live):
-        if g is not None and tuple(g.shape) != (C, H, W):
-            raise _lib.DmvsError(f"warp_corr_backward_det: gradient {tuple(g.shape)}, expected {(C, H, W)}")
-    _req(ref_q4, proj12, depth_dhw, gsim, gref, *src_q4, *live)
-    if gref is None and not live:
-        return
-    need = warp_corr_backward_det_workspace(C, H, W, len(live)) if live else 0
-    if live and workspace is None:
-        workspace = torch.empty((need // 8,), dtype=torch.int64, device=ref_q4.device)
-    nbytes = 0
-    if workspace is not None:
-        if not (workspace.is_cuda and workspace.dtype == torch.int64 and workspace.is_contiguous()):
-            raise _lib.DmvsError("warp_corr_backward_det: the workspace must be a contiguous int64 HIP tensor")
-        nbytes = workspace.numel() * 8
-    arr = (ctypes.c_void_p * nsrc)(*[s.data_ptr() for s in src_q4])
-    garr = (ctypes.c_void_p * nsrc)(*[None if g is None else g.data_ptr() for g in gsrc])
-    _lib.check(_lib.load().dmvs_warp_corr_backward_det(_ptr(ref_q4), arr, nsrc, _ptr(proj12), _ptr(depth_dhw), _ptr(gsim), _ptr(gref),
-                                                       garr, C, D, H, W, _ptr(workspace), nbytes, int(variant), _stream()),
-               "dmvs_warp_corr_backward_det")
+    _warp_corr_backward("warp_corr_backward_det", ref_q4, src_q4, proj12, depth_dhw, gsim, gref, gsrc, workspace, variant, True)
 
 
 def warp_corr(ref: torch.Tensor, src: Sequence[torch.Tensor], proj12: torch.Tensor, depth_dhw: torch.Tensor,

@@ -209,10 +209,11 @@ int dmvs_warp_corr_backward(const float* ref_q4, const float* const* src_q4, int
                             int C, int D, int H, int W, dmvs_stream_t stream);
 
 /* K1b, deterministic mode (additive, same version): dmvs_warp_corr_backward with the source gradients accumulated in FIXED
- * POINT (csrc/warp_corr_bwd_det.h; docs/kernels/K1b_warp_corr_backward.md, "Deterministic mode").  Every addend
- * t = w_tap * ((gsim * 2/C) * ref) -- the fp32 addend of the entry above -- is added as the 64-bit integer rint(t * 2^k) with an
- * integer atomic, and a finalize kernel WRITES every element of every wanted gsrc as (float)((double)sum * 2^-k): the
- * result is a pure function of the inputs, whatever the arrival order, the launch decomposition or the set of wanted views.
+ * POINT (the entry above's scatter kernel on the FixedSink of csrc/warp_corr_bwd_det.h; docs/kernels/K1b_warp_corr_backward.md,
+ * "Deterministic mode").  Every addend t = w_tap * ((gsim * 2/C) * ref) -- the fp32 addend of the entry above, formed by the
+ * same code -- is added as the 64-bit integer rint(t * 2^k) with an integer atomic, and a finalize kernel WRITES every
+ * element of every wanted gsrc as (float)((double)sum * 2^-k): the result is a pure function of the inputs, whatever the
+ * arrival order, the launch decomposition or the set of wanted views.
  *   k          one per launch: min(62 - ceil(log2(D H W)), 50) - (eg + er + 2 + log2(2 / C)) with eg, er = floor(log2(max|.|))
  *              of gsim_2dhw and of ref_q4, taken by a pre-pass on the device (no host read-back: the entry can be captured
  *              in a graph).  A maximum of zero: every gsrc element is 0.  A maximum that is not finite (or addends that may

@@ -212,7 +212,8 @@ def det_parts(ops, q4, proj12, depth, gsim, V, C, H, W, args):
             for _ in range(args.reps):
                 run()
             torch.cuda.synchronize()
-        keys = {"prepass": "det_absmax", "scatter": "det_src", "finalize": "det_finalize", "clear": "emset"}
+        # the scatter is warp_corr_bwd_src_kernel<..., FixedSink>: the sink's name is in the mangled and in the demangled form
+        keys = {"prepass": "det_absmax", "scatter": "FixedSink", "finalize": "det_finalize", "clear": "emset"}
         acc = {k: 0.0 for k in keys}
         for ev in prof.key_averages():
             t = getattr(ev, "device_time_total", None)

@@ -1,4 +1,5 @@
-"""CPU emulation of K1b's deterministic mode (csrc/warp_corr_bwd_det.h; the contract in docs/kernels/K1b_warp_corr_backward.md,
+"""CPU emulation of K1b's deterministic mode (``warp_corr_bwd_src_kernel`` of csrc/warp_corr_bwd.h on the ``FixedSink`` of
+csrc/warp_corr_bwd_det.h; the contract in docs/kernels/K1b_warp_corr_backward.md,
 "Deterministic mode"): the source-view gradients of tests/warp_corr_grad_ref.py accumulated in FIXED POINT, in torch int64.
 
   addend    t = w_tap * ((gsim * 2/C) * ref) in fp32, two separately rounded products, from the yardstick's own taps

@@ -1,6 +1,7 @@
 """CPU: the boundary of K1b's deterministic mode -- the two C entries are declared and exported under the unchanged ABI version, the
-workspace size is the int64 sums and nothing else, and the Python wrapper refuses what it cannot launch with ``DmvsError`` (no GPU
-is touched: every refusal happens before a launch)."""
+workspace size is the int64 sums and nothing else, both Python wrappers (one validation body) refuse what they cannot launch with a
+``DmvsError`` that names the public function, and both C entries (one entry body) answer the same code for the same bad argument list
+(no GPU is touched: every refusal happens before a launch)."""
 import inspect
 import os
 import re
@@ -51,40 +52,71 @@ def test_wrapper_mirrors_the_atomic_one():
     assert b["variant"].default == 0 and b["workspace"].default is None
 
 
-def test_wrapper_refuses_cpu_tensors():
+WRAPPERS = ("warp_corr_backward", "warp_corr_backward_det")   # one validation body: both refuse the same, each under its own name
+
+
+def refused(what, args, match=None):
     from dmvsnet_amd import ops
     from dmvsnet_amd._lib import DmvsError
-    with pytest.raises(DmvsError, match="HIP device"):
-        ops.warp_corr_backward_det(**_args())
+    with pytest.raises(DmvsError, match=match or rf"\b{what}: "):
+        getattr(ops, what)(**args)
+
+
+def test_wrapper_refuses_cpu_tensors():
+    for what in WRAPPERS:
+        refused(what, _args(), match="HIP device")
 
 
 @pytest.mark.parametrize("field,shape", [("gsim", (2, 4, 9, 33)), ("gsim", (1, 3, 9, 33)), ("proj12", (3, 12)), ("proj12", (2, 9)),
                                          ("depth_dhw", (1, 3, 9, 33)), ("gref", (4, 9, 33)), ("ref_q4", (9, 33, 8)),
                                          ("ref_q4", (2, 9, 32, 4))])
 def test_wrapper_refuses_wrong_shapes(field, shape):
-    from dmvsnet_amd import ops
-    from dmvsnet_amd._lib import DmvsError
-    a = _args()
-    a[field] = torch.zeros(shape)
-    with pytest.raises(DmvsError, match="warp_corr_backward_det"):
-        ops.warp_corr_backward_det(**a)
+    for what in WRAPPERS:
+        a = _args()
+        a[field] = torch.zeros(shape)
+        refused(what, a)
 
 
 def test_wrapper_refuses_wrong_lists_and_workspaces():
-    from dmvsnet_amd import ops
-    from dmvsnet_amd._lib import DmvsError
-    a = _args()
-    a["gsrc"] = a["gsrc"][:1]
-    with pytest.raises(DmvsError, match="warp_corr_backward_det"):
-        ops.warp_corr_backward_det(**a)
-    a = _args()
-    a["gsrc"][1] = torch.zeros((8, 9, 32))
-    with pytest.raises(DmvsError, match="warp_corr_backward_det"):
-        ops.warp_corr_backward_det(**a)
-    a = _args()
-    a["src_q4"][0] = torch.zeros((2, 9, 34, 4))
-    with pytest.raises(DmvsError, match="warp_corr_backward_det"):
-        ops.warp_corr_backward_det(**a)
+    for what in WRAPPERS:
+        a = _args()
+        a["gsrc"] = a["gsrc"][:1]
+        refused(what, a)
+        a = _args()
+        a["gsrc"][1] = torch.zeros((8, 9, 32))
+        refused(what, a)
+        a = _args()
+        a["src_q4"][0] = torch.zeros((2, 9, 34, 4))
+        refused(what, a)
+
+
+def test_both_c_entries_refuse_the_same_before_any_launch():
+    """The raw entries on host dummies: every case below returns before a HIP call, and nothing is dereferenced before it."""
+    import ctypes
+    from dmvsnet_amd import _lib
+    lib = _lib.load()
+    dummy = (ctypes.c_float * 16)()
+    p = ctypes.cast(dummy, ctypes.c_void_p)
+    views = lambda *ps: (ctypes.c_void_p * len(ps))(*ps)   # noqa: E731
+
+    def call(det, ref=p, src=None, nsrc=2, gsrc=None, C=8, D=3, H=9, W=33, ws=None, ws_bytes=0, variant=0):
+        src = views(*[p] * min(max(nsrc, 1), 17)) if src is None else src
+        head = (ref, src, nsrc, p, p, p, p, gsrc, C, D, H, W)
+        if det:
+            return lib.dmvs_warp_corr_backward_det(*head, ws, ws_bytes, variant, None)
+        return lib.dmvs_warp_corr_backward(*head, None)
+
+    table = [(dict(ref=None), _lib.EINVAL), (dict(nsrc=0), _lib.EINVAL), (dict(nsrc=17), _lib.EINVAL), (dict(D=0), _lib.EINVAL),
+             (dict(H=0), _lib.EINVAL), (dict(W=0), _lib.EINVAL), (dict(C=12), _lib.EUNSUPPORTED),
+             (dict(C=32, H=4096, W=4096), _lib.EUNSUPPORTED), (dict(src=views(p, None)), _lib.EINVAL)]
+    for kw, code in table:
+        assert call(False, **kw) == call(True, **kw) == code, kw
+    assert call(True, variant=2) == _lib.EINVAL
+    # a wanted view: the deterministic entry needs an 8-byte aligned workspace that is large enough
+    need = lib.dmvs_warp_corr_backward_det_workspace(8, 9, 33, 1)
+    odd = ctypes.c_void_p((p.value & ~7) + 4)
+    for ws, ws_bytes in ((None, need), (odd, need), (ctypes.c_void_p(p.value & ~7), need - 1)):
+        assert call(True, gsrc=views(p, None), ws=ws, ws_bytes=ws_bytes) == _lib.EINVAL, (ws, ws_bytes)
 
 
 def test_cost_agg_takes_the_keyword_and_exports_nothing_new():

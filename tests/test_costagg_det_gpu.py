@@ -1,5 +1,5 @@
-"""K1b's deterministic mode (csrc/warp_corr_bwd_det.h: max pre-pass, fixed-point scatter, finalize) on the MI355X, through
-``ops.warp_corr_backward_det`` and ``cost_agg(..., deterministic=...)``.
+"""K1b's deterministic mode (max pre-pass, ``warp_corr_bwd_src_kernel`` on csrc/warp_corr_bwd_det.h's ``FixedSink``, finalize) on the
+MI355X, through ``ops.warp_corr_backward_det`` and ``cost_agg(..., deterministic=...)``.
 
   bits       on the cases where fp32 forms the tap weights exactly (``costagg_det_ref.exact_names``: CONTENTION and the half-pixel AFFINE
              offsets; tests/test_costagg_det_cpu.py asserts the exactness on every one) each dSrc_v equals the CPU emulation of the
@@ -8,8 +8,8 @@
              that truncation is told apart there and not on the plain cases).
   order      SHAPES, VIEWS, SCATTER, SPECIAL, CONTENTION: two launches of variant 0 and one of variant 1 (planes in reverse, chunks of 4,
              workgroups in reverse) give the same bits; dRef equals ``ops.warp_corr_backward``'s bit for bit.
-  parity     every table under ``warp_corr_grad_ref.reference`` / ``bounds_of`` through test_warp_corr_grad_gpu.py's own ``compare`` (the
-             module is imported for it and for its cached references, which are computed once for both files): WINDOWS the mean bound
+  parity     every table under ``warp_corr_grad_ref.reference`` / ``bounds_of`` through tests/k1b_gpu_harness.py's ``compare`` (the
+             harness both K1b files import, with its cached references, which are computed once for both): WINDOWS the mean bound
              only, CONTENTION the PLAIN bound -- allowance 0, which the atomic path cannot promise.  EDGE_SHAPES: exact zeros.
   guards     every gsrc is a NaN-filled view between 1024 sentinel elements (``launch``): afterwards the guards hold their bits, every
              wanted element is finite (so: written), a view not asked for is still all NaN.  Views 0, 7, 15 of 16 alone equal the
@@ -27,16 +27,20 @@ import pytest
 import torch
 
 import costagg_det_ref as DR
-import test_warp_corr_grad_gpu as T   # helpers and the cached float64 references only; its tests are not collected from here
-import warp_corr_grad_ref as GR
+import k1b_gpu_harness as T   # the harness and the cached float64 references, computed once for both K1b files
+from k1b_gpu_harness import BY_TABLE, CASES
 
 pytestmark = pytest.mark.gpu
 
-F32 = torch.float32
-CASES = GR.all_cases()
-BY_TABLE = {t: [n for n, c in CASES.items() if c["table"] == t] for t in GR.TABLES}
 ORDER = [n for t in ("SHAPES", "VIEWS", "SCATTER", "SPECIAL", "CONTENTION") for n in BY_TABLE[t]]
 EXACT = DR.exact_names()
+launch = functools.partial(T.launch, mode="det")   # every gsrc starts as NaN inside SENTINEL guards
+
+
+@pytest.fixture(scope="module", autouse=True)
+def worst_ratios():
+    yield
+    T.print_worst("det", "det cost_agg")
 
 
 def bits(t):
@@ -45,34 +49,6 @@ def bits(t):
 
 def same_bits(a, b):
     return torch.equal(bits(a), bits(b))
-
-
-def launch(name, gsim=None, feats=None, want_ref=True, want=None, variant=0, workspace=None, expect="finite"):
-    """One guarded launch -> (gref or None, [gsrc_v or None]).  Every buffer starts as NaN inside SENTINEL guards.  ``expect``: what
-    every wanted gsrc must be afterwards ("finite" or "nan")."""
-    from dmvsnet_amd import ops
-    c = CASES[name]
-    C, (D, H, W) = c["C"], c["depth"].shape
-    feats = T.dev_feats(name) if feats is None else feats
-    nsrc = len(feats) - 1
-    want = set(range(nsrc)) if want is None else set(want)
-    gsim = c["gsim"] if gsim is None else gsim
-    rbuf, gref = T.guarded(C, H, W, float("nan"))
-    sbufs = [T.guarded(C, H, W, float("nan")) for _ in range(nsrc)]
-    ops.warp_corr_backward_det(feats[0], feats[1:], T.p12_of(name).cuda(), c["depth"].cuda(), gsim.cuda(), gref if want_ref else None,
-                               [g if v in want else None for v, (_, g) in enumerate(sbufs)], workspace=workspace, variant=variant)
-    torch.cuda.synchronize()
-    assert T.guards_intact(rbuf), f"{name}: wrote outside gref"
-    assert torch.isnan(gref).all() if not want_ref else True, f"{name}: gref touched though not asked for"
-    for v, (buf, g) in enumerate(sbufs):
-        assert T.guards_intact(buf), f"{name}: wrote outside gsrc[{v}]"
-        if v not in want:
-            assert torch.isnan(g).all(), f"{name}: gsrc[{v}] touched though not asked for"
-        elif expect == "finite":
-            assert torch.isfinite(g).all(), f"{name}: gsrc[{v}] has elements that were not written (or are not finite)"
-        else:
-            assert torch.isnan(g).all(), f"{name}: gsrc[{v}] is not all NaN"
-    return (gref if want_ref else None), [g if v in want else None for v, (_, g) in enumerate(sbufs)]
 
 
 @functools.lru_cache(maxsize=None)
