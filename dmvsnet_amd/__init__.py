@@ -25,6 +25,9 @@ from .regnet import DiffCostRegNet, DiffCostRegNetPart, DiffCostRegNetPartRefine
 from . import featurenet  # noqa: F401  (the differentiable FeatureNet: K3 + K3f for its rectangular layers, the whole network)
 from .featurenet import DiffFeatureConv2d, DiffFeatureConvBlock2d, DiffFeatureNet  # noqa: F401
 
+from . import train  # noqa: F401  (the training model: the parts above assembled into the reference's MVSNet, and one training step)
+from .train import DiffMVSNet, train_step  # noqa: F401
+
 from . import eval_io  # noqa: F401  (PFM / cam I/O, eval dataset, Model.test step 1)
 from . import fusion   # noqa: F401  (geometric-consistency fusion filter, PLY)
 from . import cloud_eval  # noqa: F401  (DTU accuracy / completeness of a fused cloud)
@@ -39,4 +42,5 @@ __all__ = ["MVSNet", "CostAgg", "CostRegNet", "DepthNet", "FeatureNet", "ViewFea
            "DiffConvTranspose2d", "bn", "DiffBatchNormReLU3d", "DiffBatchNormReLU2d", "DiffSyncBatchNormReLU3d",
            "DiffSyncBatchNormReLU2d", "convert_sync_batchnorm", "DiffConvBlock3d", "DiffDeconvBlock3d",
            "DiffConvBlock2d", "DiffDeconvBlock2d", "regnet", "DiffCostRegNetPart", "DiffCostRegNetPartRefine", "DiffCostRegNet",
-           "DiffCostRegNetRefine", "featurenet", "DiffFeatureConv2d", "DiffFeatureConvBlock2d", "DiffFeatureNet"]
+           "DiffCostRegNetRefine", "featurenet", "DiffFeatureConv2d", "DiffFeatureConvBlock2d", "DiffFeatureNet", "train",
+           "DiffMVSNet", "train_step"]

@@ -408,8 +408,8 @@ class MVSNet(nn.Module):
     # -- lifecycle ---------------------------------------------------------------------------------
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError("dmvsnet_amd.MVSNet is the inference hot path; the differentiable parts exist (DiffFeatureNet, DiffCostAgg, "
-                                      "DiffCostRegNet, DiffDepthNet), their assembly into a training model does not")
+            raise NotImplementedError("dmvsnet_amd.MVSNet is the inference hot path; the model to train is dmvsnet_amd.DiffMVSNet (the same "
+                                      "constructor arguments and state-dict keys: DiffFeatureNet, DiffCostAgg, DiffCostRegNet, DiffDepthNet assembled)")
         return super().train(False)
 
     def _invalidate(self):

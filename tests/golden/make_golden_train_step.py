@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""Generate tests/golden/op_train_step.npz by RUNNING THE REFERENCE's MVSNet in train mode on the CPU, once in float64 and once in fp32.
+
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_train_step.py <path of the reference checkout>
+
+Imports networks/mvsnet.py of the reference (read-only, never copied).  The float64 run rebinds ``torch.float32`` to ``torch.float64``
+and sets the default dtype for the duration of the call, because ``homo_warping`` hard-codes fp32 (networks/module.py:227, :248); the
+script asserts that the outputs come back float64.  Case ``train_step_ref.CASES["b2_32x32"]``: B = 2, V = 3, 32 x 32, ``ndepths`` (8, 8,
+8), ratios (4, 2, 1), ``train_step_ref.make_state_dict`` (synth weights, the gain of 20 on ``*.prob.weight`` taken out).  The loss is
+``train_step_ref.linear_functional``: a seeded linear functional of every stage's ``depth_sub_plus`` and ``depth_sub_plus_refine``.
+
+Stored, data only:
+
+* ``out.stageK.<name>``     the float64 stage outputs (``train_step_ref.STAGE_OUTPUTS`` without the hypothesis volume ``depth_values``);
+* ``buf.<key>``             every BatchNorm's running buffers and ``num_batches_tracked`` after the step;
+* ``grad.<key>``            every BatchNorm weight / bias gradient, and the weight gradients of every ``conv0`` and ``prob``;
+* ``digest.<key>``          (sum, L2 norm, dot with ``train_step_ref.digest_vector``) of all 403 parameter gradients;
+* ``fp32.out`` / ``fp32.grad``   the fp32 run's distances to the float64 run, for the record (max-abs over max-abs: per stage output in
+                            the order stored, per parameter in ``named_parameters`` order);
+* ``descent.*``             for tests/test_train_step_gpu.py: learning rate, number of Adam steps (<= 10) and the losses of
+                            ``StockMVSNet(float32)`` trained on case ``b2_32x64`` with ``train_step_ref.stock_loss``, chosen as the
+                            first pair of the table below at which the loss falls by at least 10 %.
+
+Before writing, the script runs ``StockMVSNet(float64)`` (the product's wiring function over stock parts) on the same case, prints its
+largest distance to the reference's float64 run over everything stored, and REFUSES to write the file when that exceeds 1e-9.
+"""
+import contextlib
+import io
+import os
+import sys
+import warnings
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if len(sys.argv) != 2 or not os.path.isfile(os.path.join(sys.argv[1], "networks", "mvsnet.py")):
+    sys.exit(__doc__)
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, sys.argv[1])
+warnings.filterwarnings("ignore")
+
+import train_step_ref as T  # noqa: E402
+
+with contextlib.redirect_stdout(io.StringIO()):
+    from networks import mvsnet as ref_mvsnet  # noqa: E402
+
+torch.set_num_threads(8)
+FP32, FP64 = torch.float32, torch.float64
+CASE = "b2_32x32"
+TOL = 1e-9
+MAX_BYTES = 1 << 20
+DESCENT_TABLE = [(lr, n) for n in (5, 10) for lr in (1e-3, 3e-3, 1e-2)]
+
+
+@contextlib.contextmanager
+def everything_float64():
+    torch.float32 = FP64
+    torch.set_default_dtype(FP64)
+    try:
+        yield
+    finally:
+        torch.float32 = FP32
+        torch.set_default_dtype(FP32)
+
+
+def stored_grad(key):
+    return ".bn." in key or key.endswith("conv0.conv.weight") or key.endswith("prob.weight") or key == "feature.conv0.0.conv.weight"
+
+
+def run_reference(sd, inputs, weights, dtype):
+    with contextlib.redirect_stdout(io.StringIO()):
+        net = ref_mvsnet.MVSNet(list(T.NDEPTHS), list(T.RATIOS))
+    net.load_state_dict(sd, strict=True)
+    net = net.to(dtype).train()
+    imgs, proj, dv = inputs
+    args = (imgs.to(dtype), {k: v.to(dtype) for k, v in proj.items()}, dv.to(dtype))
+    with (everything_float64() if dtype == FP64 else contextlib.nullcontext()):
+        outputs = net(*args)
+        loss = T.linear_functional(outputs, weights)
+        loss.backward()
+    for s in range(3):
+        for name in T.DIFF_OUTPUTS:
+            assert outputs[f"stage{s + 1}"][name].dtype == dtype, (s, name, outputs[f"stage{s + 1}"][name].dtype)
+    return outputs, {n: p.grad for n, p in net.named_parameters()}, T.bn_buffers(net)
+
+
+def stage_rows(outputs):
+    return [(f"stage{s + 1}.{name}", outputs[f"stage{s + 1}"][name].detach()) for s in range(3) for name in T.STAGE_OUTPUTS if name != "depth_values"]
+
+
+def descent(sd):
+    kw = T.CASES["b2_32x64"]
+    inputs, (gt, mask) = T.make_inputs(**kw), T.make_ground_truth(**kw)
+    for lr, n in DESCENT_TABLE:
+        net = T.stock_model(sd, FP32)
+        opt = torch.optim.Adam(net.parameters(), lr=lr)
+        losses = []
+        for _ in range(n + 1):   # n steps, and the loss after the last one
+            loss = T.stock_loss(net(*inputs), gt, mask)
+            losses.append(float(loss))
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+        print(f"descent lr {lr:g} N {n}: {losses[0]:.4f} -> {losses[-1]:.4f} ({1 - losses[-1] / losses[0]:+.1%})")
+        if losses[-1] <= 0.9 * losses[0]:
+            return lr, n, losses
+    sys.exit("no (lr, N) of the table makes the loss fall by 10 %")
+
+
+def main():
+    kw = T.CASES[CASE]
+    inputs, weights, sd = T.make_inputs(**kw), T.functional_weights(**kw), T.make_state_dict(kw["seed"])
+    out64, g64, buf64 = run_reference(sd, inputs, weights, FP64)
+    out32, g32, _ = run_reference(sd, inputs, weights, FP32)
+    assert len(g64) == 403 and all(g is not None for g in g64.values())
+
+    arrs = {}
+    for key, t in stage_rows(out64):
+        arrs[f"out.{key}"] = t.numpy()
+    for key, b in buf64.items():
+        arrs[f"buf.{key}"] = b.numpy()
+    for key, g in g64.items():
+        if stored_grad(key):
+            arrs[f"grad.{key}"] = g.numpy()
+        arrs[f"digest.{key}"] = T.digests(g, key)
+    arrs["fp32.out"] = np.array([T.rel_dist(a, b) for (_, a), (_, b) in zip(stage_rows(out32), stage_rows(out64))])
+    arrs["fp32.grad"] = np.array([T.rel_dist(g32[k], g64[k]) for k in g64])
+    print(f"fp32 reference vs float64 reference: outputs max {arrs['fp32.out'].max():.2e}; gradients median {np.median(arrs['fp32.grad']):.2e} "
+          f"p90 {np.quantile(arrs['fp32.grad'], 0.9):.2e} max {arrs['fp32.grad'].max():.2e}")
+
+    # the wiring function over stock parts against the reference, float64 against float64
+    net = T.stock_model(sd, FP64)
+    outs, gs, _ = T.run_step(net, inputs, lambda o: T.linear_functional(o, weights))
+    worst = max([T.rel_dist(a, b) for (_, a), (_, b) in zip(stage_rows(outs), stage_rows(out64))]
+                + [T.rel_dist(gs[k], g64[k]) for k in g64]
+                + [T.rel_dist(b.double(), buf64[k].double()) for k, b in T.bn_buffers(net).items()])
+    print(f"StockMVSNet(float64) vs the reference in float64: largest distance {worst:.2e} (limit {TOL:g})")
+    if not worst <= TOL:
+        sys.exit("refusing to write the fixture: the yardstick does not reproduce the reference")
+
+    lr, n, losses = descent(sd)
+    arrs["descent.lr"], arrs["descent.steps"], arrs["descent.losses"] = np.float64(lr), np.int64(n), np.array(losses)
+
+    path = os.path.join(HERE, "op_train_step.npz")
+    np.savez_compressed(path, **arrs)
+    size = os.path.getsize(path)
+    print(f"wrote {path}: {len(arrs)} arrays, {size} bytes")
+    assert size < MAX_BYTES, size
+
+
+if __name__ == "__main__":
+    main()

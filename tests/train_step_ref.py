@@ -1,0 +1,344 @@
+"""Yardstick of the whole training step (dmvsnet_amd.train): ``StockMVSNet(dtype)``, the product's ONE wiring function
+``dmvsnet_amd.train.wire`` over stock ATen parts on the CPU, and ``ForcedDecisions``.  No product kernel runs here.
+
+``StockMVSNet(float64)`` is the yardstick, ``StockMVSNet(float32)`` the ``e_ref`` arm.  tests/test_train_step_cpu.py holds the float64
+form to a float64 run of the reference's own ``MVSNet`` (tests/golden/op_train_step.npz) to 1e-9: that certifies the wiring function and
+this file together; everything on the GPU is then held to this file.
+
+The parts, from the helpers that exist:
+
+* ``featurenet_grad_ref.StockFeatureNet``, ``regnet_grad_ref.PlainPair`` (``PlainPart`` / ``PlainPartRefine`` as pairs): stock nn layers
+  with the reference's children and state-dict keys;
+* ``hypotheses_ref.first`` / ``later``, per sample (the product's documented deviation: every sample from its own depth range);
+* cost aggregation: ``costagg_grad_ref.cost_agg_f64`` in float64.  That helper is pinned to float64, so the fp32 arm runs ``cost_agg``
+  below: the same lines with the dtype as an argument (the CPU test asserts that in float64 the two are the same bits);
+* head: ``head_grad_ref.regress_forward`` for the values.  Its backward is ``head_grad_ref.regress_backward``, the closed form, because
+  that is the one that takes ``route_dsp``: the expectations that decide which channel of a pair the min / max gradient goes to.  With
+  recorded ``depth_sub_plus`` of another run there, that run's routing decisions are forced; without, the run's own are used and the
+  result is autograd's (asserted by tests/test_head_grad_cpu.py, and again by the 1e-9 test against the reference).  The two
+  confidences, which ``head_grad_ref`` does not restate, are the reference's lines (networks/mvsnet.py:59-62) written out.
+
+``ForcedDecisions`` records, per BatchNorm module (by its state-dict prefix, which ``DiffMVSNet`` and ``StockMVSNet`` share) and per call
+(FeatureNet is called V times), the mask ``output > 0`` -- for a stock BatchNorm that is the ReLU decision of the block around it, for the
+product's fused BatchNorm + ReLU module it is the same mask taken from the block's output -- and replays a recorded set: a forward hook
+returns ``where(mask, |y|, -|y|)`` with an identity backward, so the ReLU behind it takes the recorded side.  Why: at these tiny
+volumes 2 to 8 of the 3.5 million ReLU decisions of a step fall on different sides of the kink in an fp32 and a float64 run, one voxel
+moves a stage-1 weight gradient by a percent, and a per-tensor gradient comparison without forced decisions is a coin toss.
+
+All cases use ``synth`` inputs and ``synth_state_dict`` with every ``*.prob.weight`` divided by 20: the recipe's gain of 20 makes the
+softmaxes sharp, and with ``alpha = 5`` in the refine pass and hypotheses extrapolated five-fold the forward is then chaotic (an fp32 and
+a float64 run of the reference differ by 2e-2 in the stage-3 depth); without the gain every stage output agrees to a few 1e-6.
+"""
+import contextlib
+
+import numpy as np
+import torch
+from torch import nn
+
+import costagg_grad_ref as CG
+import featurenet_grad_ref as FG
+import head_grad_ref as HG
+import hypotheses_ref as HY
+import regnet_grad_ref as RG
+from dmvsnet_amd import synth, train
+
+bound_of, rel_dist = RG.bound_of, RG.rel_dist
+NDEPTHS, RATIOS = (8, 8, 8), (4, 2, 1)
+DLOSSW = (0.5, 1.0, 2.0)   # the reference's recipe (scripts/train.sh)
+GROUPS = ("feature",) + tuple(f"{net}.{s}" for net in ("cost_regularization", "cost_regularization_refine") for s in range(3))
+DIFF_OUTPUTS = ("depth_sub_plus", "depth_values_c", "depth_sub_plus_refine", "depth")
+STAGE_OUTPUTS = DIFF_OUTPUTS + ("depth_values", "photometric_confidence", "photometric_confidence_refine")
+# the cases: T1 (CPU, against the reference), T3 / T4 first case, T3 second case
+CASES = {"b2_32x32": dict(B=2, V=3, H=32, W=32, ndepths=NDEPTHS, seed=0),
+         "b2_32x64": dict(B=2, V=3, H=32, W=64, ndepths=NDEPTHS, seed=0),
+         "b1_64x96": dict(B=1, V=3, H=64, W=96, ndepths=(48, 32, 8), seed=0)}
+
+
+def group_of(name):
+    return next(g for g in GROUPS if name.startswith(g + "."))
+
+
+# ------------------------------------------------------------------------------------------------ inputs
+def make_inputs(B, V, H, W, seed=0, **_):
+    """imgs [B,V,3,H,W] (another image set per sample), proj_matrices {"stageK": [B,V,2,4,4]}, depth_values [B,192]: the samples
+    share the cameras and the depth range.  fp32, CPU."""
+    imgs = torch.cat([synth.synth_images(H, W, V, seed=seed + 1000 * b) for b in range(B)])
+    proj = {k: v.repeat(B, 1, 1, 1, 1) for k, v in synth.synth_cameras(H, W, V).items()}
+    return imgs, proj, synth.synth_depth_values().repeat(B, 1)
+
+
+def make_state_dict(seed=0):
+    """``synth_state_dict`` on the model's keys with the gain of 20 on every ``*.prob.weight`` taken out (see the module's text)."""
+    sd = synth.synth_state_dict(StockMVSNet(NDEPTHS, RATIOS).state_dict(), seed)
+    return {k: (v / 20 if k.endswith("prob.weight") else v) for k, v in sd.items()}
+
+
+def make_ground_truth(B, H, W, seed=0, **_):
+    """-> (depth_gt_ms, mask_ms) {"stageK": [B,h,w]}: a smooth surface inside the depth range and a mask with holes, per stage."""
+    gt, mask = {}, {}
+    for s in range(3):
+        h, w = H >> (2 - s), W >> (2 - s)
+        g = np.random.Generator(np.random.PCG64([seed, 77, s]))
+        yy, xx = np.meshgrid(np.arange(h, dtype=np.float32) / h, np.arange(w, dtype=np.float32) / w, indexing="ij")
+        ph = g.random((B, 1, 1), dtype=np.float32)
+        surf = np.float32(640.0) + np.float32(50.0) * np.sin(np.float32(5.0) * yy[None] + ph) + np.float32(40.0) * np.cos(np.float32(4.0) * xx[None] - ph)
+        gt[f"stage{s + 1}"] = torch.from_numpy((surf + g.standard_normal((B, h, w), dtype=np.float32)).astype(np.float32))
+        mask[f"stage{s + 1}"] = torch.from_numpy((g.random((B, h, w), dtype=np.float32) > 0.1).astype(np.float32))
+    return gt, mask
+
+
+def functional_weights(B, H, W, seed=0, **_):
+    """The seeded linear functional: one weight per element of every stage's ``depth_sub_plus`` and ``depth_sub_plus_refine``."""
+    out = {}
+    for s in range(3):
+        g = np.random.Generator(np.random.PCG64([seed, 99, s]))
+        for name in ("depth_sub_plus", "depth_sub_plus_refine"):
+            out[f"stage{s + 1}.{name}"] = torch.from_numpy(g.standard_normal((B, 4, H >> (2 - s), W >> (2 - s)), dtype=np.float32))
+    return out
+
+
+def linear_functional(outputs, weights):
+    """sum over the stages of <w, depth_sub_plus> + <w', depth_sub_plus_refine>: a loss with no kinks of its own."""
+    total = 0
+    for key, w in weights.items():
+        stage, name = key.split(".")
+        t = outputs[stage][name]
+        total = total + (t * w.to(t.device, t.dtype)).sum()
+    return total
+
+
+def stock_loss(outputs, depth_gt_ms, mask_ms, dlossw=DLOSSW):
+    """``diff_mvs_loss`` on the CPU under autograd: ``head_grad_ref.loss_set`` (the product's definition of the dual-depth loss) over
+    the stages, main outputs then refine outputs.  What the golden script trains ``StockMVSNet(float32)`` with."""
+    total = 0
+    for s in range(3):
+        key = f"stage{s + 1}"
+        for name in ("depth_sub_plus", "depth_sub_plus_refine"):
+            t = outputs[key][name]
+            total = total + HG.loss_set(t, depth_gt_ms[key].to(t.dtype), mask_ms[key], float(dlossw[s]))
+    return total
+
+
+# ------------------------------------------------------------------------------------------------ the stock parts
+def cost_agg(features, proj_matrices, depth_values, dtype):
+    """``costagg_grad_ref.cost_agg_f64`` (CostAgg.forward over homo_warping, networks/mvsnet.py:111-153, module.py:212-251) with the
+    dtype as an argument: the fp32 arm.  Same lines, same order."""
+    feats = [f.to(dtype) for f in features]
+    proj, depth = proj_matrices.detach().to(dtype), depth_values.detach().to(dtype)
+    ref = feats[0]
+    B, C, H, W = ref.shape
+    D = depth.shape[1]
+    total = 0
+    with torch.no_grad():
+        def compose(pair):
+            P = pair[:, 0].clone()
+            P[:, :3, :4] = pair[:, 1, :3, :3] @ pair[:, 0, :3, :4]
+            return P
+        ref_inv = torch.inverse(compose(proj[:, 0]))
+        yy, xx = torch.meshgrid(torch.arange(H, dtype=dtype, device=ref.device), torch.arange(W, dtype=dtype, device=ref.device), indexing="ij")
+        xyz = torch.stack((xx.reshape(-1), yy.reshape(-1), torch.ones(H * W, dtype=dtype, device=ref.device)))
+    for v in range(1, len(feats)):
+        with torch.no_grad():
+            P = compose(proj[:, v]) @ ref_inv
+            rot, trans = P[:, :3, :3], P[:, :3, 3]
+            pts = (rot @ xyz.unsqueeze(0).expand(B, 3, H * W)).unsqueeze(2) * depth.reshape(B, 1, D, H * W) + trans.view(B, 3, 1, 1)
+            z = pts[:, 2]
+            z = torch.where(z == 0, z + 1e-5, z)
+            gx = pts[:, 0] / z / ((W - 1) / 2) - 1
+            gy = pts[:, 1] / z / ((H - 1) / 2) - 1
+            grid = torch.stack((gx, gy), dim=3).view(B, D * H, W, 2)
+        warped = nn.functional.grid_sample(feats[v], grid, mode="bilinear", padding_mode="zeros", align_corners=True).view(B, C, D, H, W)
+        total = total + (warped.view(B, C // 2, 2, D, H, W) * ref.view(B, C // 2, 2, 1, H, W)).mean(1)
+    return total
+
+
+class _Head(torch.autograd.Function):
+    """``head_grad_ref.regress_forward`` with ``head_grad_ref.regress_backward`` behind it; ``route`` (or None): the expectations that
+    decide the min / max routing of the backward."""
+
+    @staticmethod
+    def forward(ctx, logits, hyp, alpha, mode, route):
+        ctx.save_for_backward(logits, hyp)
+        ctx.alpha, ctx.mode, ctx.route = alpha, mode, route
+        ctx.set_materialize_grads(False)
+        return HG.regress_forward(logits, hyp, alpha, mode)
+
+    @staticmethod
+    def backward(ctx, g_dsp, g_sel):
+        logits, hyp = ctx.saved_tensors
+        if g_dsp is None and g_sel is None:
+            return None, None, None, None, None
+        route = None if ctx.route is None else ctx.route.to(logits.device, logits.dtype)
+        g_logits, g_hyp = HG.regress_backward(logits, hyp, ctx.alpha, ctx.mode, g_dsp, g_sel, route_dsp=route)
+        return g_logits, g_hyp, None, None, None
+
+
+def _confidence(dsp, interval):
+    with torch.no_grad():   # networks/mvsnet.py:59-62
+        return 2 * (torch.sigmoid(interval / (dsp.var(1, unbiased=False).sqrt() + 1e-5)) - 0.5)
+
+
+class StockMVSNet(nn.Module):
+    """The reference's ``MVSNet`` as ``dmvsnet_amd.train.wire`` over stock parts, in ``dtype`` on the CPU; children and state-dict keys
+    are the reference's (``cost_aggregation`` and ``DepthNet`` own no parameters and are not modules here).  ``routes``: {(stage index,
+    "main" | "refine"): recorded depth_sub_plus} for the head's backward (``ForcedDecisions.routes_of``)."""
+
+    def __init__(self, ndepths=NDEPTHS, depth_interval_ratio=RATIOS, dtype=torch.float64, inverse_depth=False):
+        super().__init__()
+        self.ndepths, self.depth_interval_ratio, self.inverse_depth, self.dtype = list(ndepths), list(depth_interval_ratio), inverse_depth, dtype
+        self.feature = FG.StockFeatureNet()
+        self.cost_regularization = nn.ModuleList([RG.PlainPair(False) for _ in ndepths])
+        self.cost_regularization_refine = nn.ModuleList([RG.PlainPair(True) for _ in ndepths])
+        self.routes = None
+        self.hypotheses = None   # (first, next) in place of hypotheses_ref's, which compute on the CPU: scripts/train_step_bench.py
+        self.to(dtype)
+
+    def parts(self):
+        dt = self.dtype
+        stage = {"main": 0, "refine": 0}
+
+        def route(which):   # the heads are called once per stage, in stage order
+            s = stage[which]
+            stage[which] += 1
+            return None if self.routes is None else self.routes[(s, which)]
+
+        def head(cost_reg, hyp, interval):
+            dsp, c = _Head.apply(cost_reg, hyp, 1.0, 0, route("main"))
+            return {"photometric_confidence": _confidence(dsp, interval), "depth_sub_plus": dsp, "depth_values_c": c, "depth_values": hyp,
+                    "interval": interval}
+
+        def head_refine(cost_reg, hyp_c, interval):
+            dsp, depth = _Head.apply(cost_reg, hyp_c, HG.REFINE_ALPHA, 1, route("refine"))
+            return {"depth": depth, "photometric_confidence_refine": _confidence(dsp, interval), "depth_sub_plus_refine": dsp}
+
+        def hypotheses_first(depth_values, D, h, w, inverse):
+            per = [HY.first(dv, D, h, w, inverse, dt) for dv in depth_values]
+            return torch.stack([p for p, _ in per]), per[0][1]
+
+        def hypotheses_next(last_depth, depth_values, ratio, D, inverse):
+            per = [HY.later(ld, dv, ratio, D, inverse, 2, dt) for ld, dv in zip(last_depth, depth_values)]
+            return torch.stack([p for p, _ in per]), per[0][1]
+
+        if self.hypotheses is not None:
+            hypotheses_first, hypotheses_next = self.hypotheses
+        agg = CG.cost_agg_f64 if dt == torch.float64 else (lambda f, p, d: cost_agg(f, p, d, dt))
+        return train.Parts(feature=self.feature, cost_agg=agg, regnet=self.cost_regularization, regnet_refine=self.cost_regularization_refine,
+                           head=head, head_refine=head_refine, hypotheses_first=hypotheses_first, hypotheses_next=hypotheses_next)
+
+    def forward(self, imgs, proj_matrices, depth_values):
+        return train.wire(self.parts(), imgs.to(self.dtype), proj_matrices, depth_values, self.ndepths, self.depth_interval_ratio,
+                          self.inverse_depth)
+
+
+def stock_model(sd, dtype, ndepths=NDEPTHS, ratios=RATIOS, train_mode=True):
+    net = StockMVSNet(ndepths, ratios, torch.float32)
+    net.load_state_dict(sd, strict=True)
+    net = net.to(dtype)
+    net.dtype = dtype
+    return net.train(train_mode)
+
+
+# ------------------------------------------------------------------------------------------------ forced decisions
+class _Force(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, mask):
+        a = y.abs()
+        return torch.where(mask, a, -a)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+class ForcedDecisions:
+    """``masks``: {BatchNorm module name: [mask of call 0, mask of call 1, ...]} (bool, CPU); ``routes``: see ``StockMVSNet``."""
+
+    def __init__(self):
+        self.masks, self.routes = {}, None
+
+    @staticmethod
+    def _batchnorms(model):
+        return [(n, m) for n, m in model.named_modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+
+    @contextlib.contextmanager
+    def record(self, model):
+        self.masks = {}
+        hooks = [m.register_forward_hook(lambda mod, inp, out, n=n: self.masks.setdefault(n, []).append((out.detach() > 0).cpu()))
+                 for n, m in self._batchnorms(model)]
+        try:
+            yield self
+        finally:
+            for h in hooks:
+                h.remove()
+
+    def routes_of(self, outputs):
+        """Keep the run's ``depth_sub_plus`` / ``depth_sub_plus_refine`` of every stage as the routing decisions of the heads."""
+        self.routes = {}
+        for s in range(3):
+            st = outputs[f"stage{s + 1}"]
+            self.routes[(s, "main")] = st["depth_sub_plus"].detach().cpu()
+            self.routes[(s, "refine")] = st["depth_sub_plus_refine"].detach().cpu()
+        return self
+
+    @contextlib.contextmanager
+    def replay(self, model):
+        calls = {}
+
+        def hook(mod, inp, out, n):
+            k = calls.get(n, 0)
+            calls[n] = k + 1
+            return _Force.apply(out, self.masks[n][k].to(out.device))
+
+        names = [n for n, _ in self._batchnorms(model)]
+        assert set(names) == set(self.masks), "the recorded run has other BatchNorm modules"
+        hooks = [m.register_forward_hook(lambda mod, inp, out, n=n: hook(mod, inp, out, n)) for n, m in self._batchnorms(model)]
+        model.routes = self.routes
+        try:
+            yield self
+        finally:
+            model.routes = None
+            for h in hooks:
+                h.remove()
+            assert all(calls.get(n, 0) == len(self.masks[n]) for n in names), "the replay made another number of calls"
+
+    def count(self):
+        return sum(int(m.numel()) for ms in self.masks.values() for m in ms)
+
+    def differing(self, other):
+        """Number of decisions in which two recorded sets differ."""
+        return sum(int((a != b).sum()) for n in self.masks for a, b in zip(self.masks[n], other.masks[n]))
+
+
+# ------------------------------------------------------------------------------------------------ runs
+def run_step(model, inputs, loss_fn, forced=None, record=None):
+    """Train-mode forward + backward on a fresh copy of no state: -> (outputs, {parameter name: gradient}).  ``loss_fn(outputs)`` -> a
+    scalar.  ``forced``: a ForcedDecisions to replay; ``record``: one to record into."""
+    for p in model.parameters():
+        p.grad = None
+    with contextlib.ExitStack() as stack:
+        if forced is not None:
+            stack.enter_context(forced.replay(model))
+        if record is not None:
+            stack.enter_context(record.record(model))
+        outputs = model(*inputs)
+    if record is not None:
+        record.routes_of(outputs)
+    loss = loss_fn(outputs)
+    loss.backward()
+    return outputs, {n: p.grad for n, p in model.named_parameters()}, loss.detach()
+
+
+def bn_buffers(model):
+    return {n: b.detach().clone() for n, b in model.named_buffers()}
+
+
+def digest_vector(name, numel):
+    """The seeded vector of a gradient's stored dot product."""
+    import zlib
+    return np.random.Generator(np.random.PCG64([zlib.crc32(name.encode()), 5])).standard_normal(numel)
+
+
+def digests(grad, name):
+    """(sum, L2 norm, dot with the seeded vector) of a gradient, in float64."""
+    g = grad.detach().double().reshape(-1).numpy()
+    return np.array([g.sum(), np.sqrt((g * g).sum()), (g * digest_vector(name, g.size)).sum()])
