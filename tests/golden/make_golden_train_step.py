@@ -1,25 +1,41 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/op_train_step.npz by RUNNING THE REFERENCE's MVSNet in train mode on the CPU, once in float64 and once in fp32.
+"""Generate the tests/golden/op_train_step*.npz files by RUNNING THE REFERENCE's MVSNet on the CPU, once in float64 and once in fp32.
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_train_step.py <path of the reference checkout>
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_train_step.py <path of the reference checkout> [case ...]
 
 Imports networks/mvsnet.py of the reference (read-only, never copied).  The float64 run rebinds ``torch.float32`` to ``torch.float64``
-and sets the default dtype for the duration of the call, because ``homo_warping`` hard-codes fp32 (networks/module.py:227, :248); the
-script asserts that the outputs come back float64.  Case ``train_step_ref.CASES["b2_32x32"]``: B = 2, V = 3, 32 x 32, ``ndepths`` (8, 8,
-8), ratios (4, 2, 1), ``train_step_ref.make_state_dict`` (synth weights, the gain of 20 on ``*.prob.weight`` taken out).  The loss is
+and sets the default dtype for the duration of the call, because ``homo_warping`` hard-codes fp32 (networks/module.py:227, :248), and
+rebinds ``torch.Tensor.float`` to ``Tensor.double``, because the inverse-depth branch of ``get_depth_range_samples`` ends in ``.float()``
+(module.py:649): without it the inverse planes are rounded to fp32 and 1e-9 cannot hold.  The script asserts that the differentiable
+outputs AND the hypothesis volume of every stage come back float64.
+
+One file per case of ``train_step_ref.FIXTURES`` (all of them when no case is named); ratios (4, 2, 1),
+``train_step_ref.make_state_dict`` (synth weights, the gain of 20 on ``*.prob.weight`` taken out).  The loss is
 ``train_step_ref.linear_functional``: a seeded linear functional of every stage's ``depth_sub_plus`` and ``depth_sub_plus_refine``.
+
+* ``b2_32x32`` (op_train_step.npz): B = 2, V = 3, 32 x 32, (8, 8, 8), linear sampling, train mode;
+* ``b2_32x32_inv``: the same with inverse-depth sampling;
+* ``b2_32x32_recipe``: the flags of scripts/train.sh -- inverse depth, (48, 32, 8), V = 5, B = 2 -- at 32 x 32, train mode;
+* ``b2_32x32_unlike``: inverse depth, every sample its own reference camera and depth range (``train_step_ref.make_inputs``).  With such a
+  batch the reference takes sample 0's intervals for every sample and the product does not (dmvsnet_amd/train.py, "One deviation"), so the
+  reference is run in EVAL mode (BatchNorm on running statistics: the samples are independent) once PER SAMPLE with B = 1, and the
+  product's batch is held to those runs.
 
 Stored, data only:
 
-* ``out.stageK.<name>``     the float64 stage outputs (``train_step_ref.STAGE_OUTPUTS`` without the hypothesis volume ``depth_values``);
-* ``buf.<key>``             every BatchNorm's running buffers and ``num_batches_tracked`` after the step;
-* ``grad.<key>``            every BatchNorm weight / bias gradient, and the weight gradients of every ``conv0`` and ``prob``;
-* ``digest.<key>``          (sum, L2 norm, dot with ``train_step_ref.digest_vector``) of all 403 parameter gradients;
+* ``out.stageK.<name>``     the float64 stage outputs (``train_step_ref.STAGE_OUTPUTS`` without the hypothesis volume ``depth_values``;
+                            the unlike case stores it too, the per-sample runs stacked along the batch axis);
+* ``buf.<key>``             every BatchNorm's running buffers and ``num_batches_tracked`` after the step (train-mode cases);
+* ``grad.<key>``            every BatchNorm weight / bias gradient, and the weight gradients of every ``conv0`` and ``prob`` (train-mode
+                            cases);
+* ``digest.<key>``          (sum, L2 norm, dot with ``train_step_ref.digest_vector``) of all 403 parameter gradients; unlike case: of the
+                            SUM of the per-sample runs' gradients;
+* ``itv.stageK``            unlike case: the ``interval`` entry of every per-sample run, [B];
 * ``fp32.out`` / ``fp32.grad``   the fp32 run's distances to the float64 run, for the record (max-abs over max-abs: per stage output in
                             the order stored, per parameter in ``named_parameters`` order);
-* ``descent.*``             for tests/test_train_step_gpu.py: learning rate, number of Adam steps (<= 10) and the losses of
-                            ``StockMVSNet(float32)`` trained on case ``b2_32x64`` with ``train_step_ref.stock_loss``, chosen as the
-                            first pair of the table below at which the loss falls by at least 10 %.
+* ``descent.*``             ``b2_32x32`` only, for tests/test_train_step_gpu.py: learning rate, number of Adam steps (<= 10) and the
+                            losses of ``StockMVSNet(float32)`` trained on case ``b2_32x64`` with ``train_step_ref.stock_loss``, chosen as
+                            the first pair of the table below at which the loss falls by at least 10 %.
 
 Before writing, the script runs ``StockMVSNet(float64)`` (the product's wiring function over stock parts) on the same case, prints its
 largest distance to the reference's float64 run over everything stored, and REFUSES to write the file when that exceeds 1e-9.
@@ -35,7 +51,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-if len(sys.argv) != 2 or not os.path.isfile(os.path.join(sys.argv[1], "networks", "mvsnet.py")):
+if len(sys.argv) < 2 or not os.path.isfile(os.path.join(sys.argv[1], "networks", "mvsnet.py")):
     sys.exit(__doc__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -49,7 +65,6 @@ with contextlib.redirect_stdout(io.StringIO()):
 
 torch.set_num_threads(8)
 FP32, FP64 = torch.float32, torch.float64
-CASE = "b2_32x32"
 TOL = 1e-9
 MAX_BYTES = 1 << 20
 DESCENT_TABLE = [(lr, n) for n in (5, 10) for lr in (1e-3, 3e-3, 1e-2)]
@@ -57,11 +72,14 @@ DESCENT_TABLE = [(lr, n) for n in (5, 10) for lr in (1e-3, 3e-3, 1e-2)]
 
 @contextlib.contextmanager
 def everything_float64():
+    assert "float" not in vars(torch.Tensor)   # inherited: deleting the override below restores it
     torch.float32 = FP64
     torch.set_default_dtype(FP64)
+    torch.Tensor.float = lambda self, *a, **k: self.double()
     try:
         yield
     finally:
+        del torch.Tensor.float
         torch.float32 = FP32
         torch.set_default_dtype(FP32)
 
@@ -70,11 +88,11 @@ def stored_grad(key):
     return ".bn." in key or key.endswith("conv0.conv.weight") or key.endswith("prob.weight") or key == "feature.conv0.0.conv.weight"
 
 
-def run_reference(sd, inputs, weights, dtype):
+def run_reference(kw, sd, inputs, weights, dtype, train_mode=True):
     with contextlib.redirect_stdout(io.StringIO()):
-        net = ref_mvsnet.MVSNet(list(T.NDEPTHS), list(T.RATIOS))
+        net = ref_mvsnet.MVSNet(list(kw["ndepths"]), list(T.RATIOS), inverse_depth=kw.get("inverse", False))
     net.load_state_dict(sd, strict=True)
-    net = net.to(dtype).train()
+    net = net.to(dtype).train(train_mode)
     imgs, proj, dv = inputs
     args = (imgs.to(dtype), {k: v.to(dtype) for k, v in proj.items()}, dv.to(dtype))
     with (everything_float64() if dtype == FP64 else contextlib.nullcontext()):
@@ -82,13 +100,14 @@ def run_reference(sd, inputs, weights, dtype):
         loss = T.linear_functional(outputs, weights)
         loss.backward()
     for s in range(3):
-        for name in T.DIFF_OUTPUTS:
+        for name in T.DIFF_OUTPUTS + ("depth_values",):
             assert outputs[f"stage{s + 1}"][name].dtype == dtype, (s, name, outputs[f"stage{s + 1}"][name].dtype)
     return outputs, {n: p.grad for n, p in net.named_parameters()}, T.bn_buffers(net)
 
 
-def stage_rows(outputs):
-    return [(f"stage{s + 1}.{name}", outputs[f"stage{s + 1}"][name].detach()) for s in range(3) for name in T.STAGE_OUTPUTS if name != "depth_values"]
+def stage_rows(outputs, names=None):
+    names = [n for n in T.STAGE_OUTPUTS if n != "depth_values"] if names is None else names
+    return [(f"stage{s + 1}.{name}", outputs[f"stage{s + 1}"][name].detach()) for s in range(3) for name in names]
 
 
 def descent(sd):
@@ -110,11 +129,19 @@ def descent(sd):
     sys.exit("no (lr, N) of the table makes the loss fall by 10 %")
 
 
-def main():
-    kw = T.CASES[CASE]
+def fp32_record(arrs, rows32, rows64, g32, g64):
+    arrs["fp32.out"] = np.array([T.rel_dist(a, b) for (_, a), (_, b) in zip(rows32, rows64)])
+    arrs["fp32.grad"] = np.array([T.rel_dist(g32[k], g64[k]) for k in g64])
+    print(f"fp32 reference vs float64 reference: outputs max {arrs['fp32.out'].max():.2e}; gradients median {np.median(arrs['fp32.grad']):.2e} "
+          f"p90 {np.quantile(arrs['fp32.grad'], 0.9):.2e} max {arrs['fp32.grad'].max():.2e}")
+
+
+def train_case(case):
+    """-> (arrays, largest distance of StockMVSNet(float64) to the reference over everything stored)."""
+    kw = T.CASES[case]
     inputs, weights, sd = T.make_inputs(**kw), T.functional_weights(**kw), T.make_state_dict(kw["seed"])
-    out64, g64, buf64 = run_reference(sd, inputs, weights, FP64)
-    out32, g32, _ = run_reference(sd, inputs, weights, FP32)
+    out64, g64, buf64 = run_reference(kw, sd, inputs, weights, FP64)
+    out32, g32, _ = run_reference(kw, sd, inputs, weights, FP32)
     assert len(g64) == 403 and all(g is not None for g in g64.values())
 
     arrs = {}
@@ -126,29 +153,79 @@ def main():
         if stored_grad(key):
             arrs[f"grad.{key}"] = g.numpy()
         arrs[f"digest.{key}"] = T.digests(g, key)
-    arrs["fp32.out"] = np.array([T.rel_dist(a, b) for (_, a), (_, b) in zip(stage_rows(out32), stage_rows(out64))])
-    arrs["fp32.grad"] = np.array([T.rel_dist(g32[k], g64[k]) for k in g64])
-    print(f"fp32 reference vs float64 reference: outputs max {arrs['fp32.out'].max():.2e}; gradients median {np.median(arrs['fp32.grad']):.2e} "
-          f"p90 {np.quantile(arrs['fp32.grad'], 0.9):.2e} max {arrs['fp32.grad'].max():.2e}")
+    fp32_record(arrs, stage_rows(out32), stage_rows(out64), g32, g64)
 
     # the wiring function over stock parts against the reference, float64 against float64
-    net = T.stock_model(sd, FP64)
+    net = T.stock_of(case, sd, FP64)
     outs, gs, _ = T.run_step(net, inputs, lambda o: T.linear_functional(o, weights))
     worst = max([T.rel_dist(a, b) for (_, a), (_, b) in zip(stage_rows(outs), stage_rows(out64))]
                 + [T.rel_dist(gs[k], g64[k]) for k in g64]
                 + [T.rel_dist(b.double(), buf64[k].double()) for k, b in T.bn_buffers(net).items()])
-    print(f"StockMVSNet(float64) vs the reference in float64: largest distance {worst:.2e} (limit {TOL:g})")
-    if not worst <= TOL:
-        sys.exit("refusing to write the fixture: the yardstick does not reproduce the reference")
+    return arrs, worst
 
-    lr, n, losses = descent(sd)
-    arrs["descent.lr"], arrs["descent.steps"], arrs["descent.losses"] = np.float64(lr), np.int64(n), np.array(losses)
 
-    path = os.path.join(HERE, "op_train_step.npz")
-    np.savez_compressed(path, **arrs)
-    size = os.path.getsize(path)
-    print(f"wrote {path}: {len(arrs)} arrays, {size} bytes")
-    assert size < MAX_BYTES, size
+def unlike_case(case):
+    """Eval mode, the reference once per sample with B = 1; see the module's text."""
+    kw = T.CASES[case]
+    (imgs, proj, dv), weights, sd = T.make_inputs(**kw), T.functional_weights(**kw), T.make_state_dict(kw["seed"])
+    names = list(T.STAGE_OUTPUTS)
+    runs = {FP64: [], FP32: []}
+    for b in range(kw["B"]):
+        one = (imgs[b:b + 1], {k: v[b:b + 1] for k, v in proj.items()}, dv[b:b + 1])
+        w_one = {k: w[b:b + 1] for k, w in weights.items()}
+        for dtype in runs:
+            outputs, grads, buffers = run_reference(kw, sd, one, w_one, dtype, train_mode=False)
+            assert all(int(v) == 0 for k, v in buffers.items() if k.endswith("num_batches_tracked"))   # eval mode updates nothing
+            runs[dtype].append((outputs, grads))
+    stacked = {dt: [(key, torch.cat([dict(stage_rows(o, names))[key] for o, _ in rs])) for key, _ in stage_rows(rs[0][0], names)]
+               for dt, rs in runs.items()}
+    summed = {dt: {k: sum(g[k] for _, g in rs) for k in rs[0][1]} for dt, rs in runs.items()}
+    assert len(summed[FP64]) == 403 and all(g is not None for g in summed[FP64].values())
+
+    arrs = {}
+    for key, t in stacked[FP64]:
+        arrs[f"out.{key}"] = t.numpy()
+    for s in range(3):
+        arrs[f"itv.stage{s + 1}"] = np.array([float(o[f"stage{s + 1}"]["interval"]) for o, _ in runs[FP64]])
+        assert arrs[f"itv.stage{s + 1}"][1:].tolist() != arrs[f"itv.stage{s + 1}"][:-1].tolist()   # unlike samples, unlike intervals
+    for key, g in summed[FP64].items():
+        arrs[f"digest.{key}"] = T.digests(g, key)
+    fp32_record(arrs, stacked[FP32], stacked[FP64], summed[FP32], summed[FP64])
+
+    # the wiring function over stock parts ON THE BATCH against the per-sample runs of the reference; the confidences of sample
+    # b > 0 against the reference's lines on its own depth_sub_plus with sample 0's interval (the documented rule)
+    net = T.stock_of(case, sd, FP64, train_mode=False)
+    outs, gs, _ = T.run_step(net, (imgs, proj, dv), lambda o: T.linear_functional(o, weights))
+    dists = [T.rel_dist(gs[k], summed[FP64][k]) for k in gs]
+    got, want = dict(stage_rows(outs, names)), dict(stacked[FP64])
+    for key in got:
+        stage, name = key.split(".")
+        for b in range(kw["B"]):
+            w = want[key][b]
+            if "confidence" in name and b > 0:
+                dsp = want[stage + "." + ("depth_sub_plus_refine" if name.endswith("refine") else "depth_sub_plus")][b:b + 1]
+                w = T.confidence(dsp, torch.tensor(arrs["itv." + stage][0], dtype=FP64))[0]
+            dists.append(T.rel_dist(got[key][b], w))
+    return arrs, max(dists)
+
+
+def main():
+    cases = sys.argv[2:] or list(T.FIXTURES)
+    assert all(c in T.FIXTURES for c in cases), (cases, list(T.FIXTURES))
+    for case in cases:
+        print(f"case {case}: {T.CASES[case]}")
+        arrs, worst = (unlike_case if T.CASES[case].get("unlike") else train_case)(case)
+        print(f"StockMVSNet(float64) vs the reference in float64: largest distance {worst:.2e} (limit {TOL:g})")
+        if not worst <= TOL:
+            sys.exit("refusing to write the fixture: the yardstick does not reproduce the reference")
+        if case == "b2_32x32":
+            lr, n, losses = descent(T.make_state_dict(T.CASES[case]["seed"]))
+            arrs["descent.lr"], arrs["descent.steps"], arrs["descent.losses"] = np.float64(lr), np.int64(n), np.array(losses)
+        path = os.path.join(HERE, T.FIXTURES[case])
+        np.savez_compressed(path, **arrs)
+        size = os.path.getsize(path)
+        print(f"wrote {path}: {len(arrs)} arrays, {size} bytes")
+        assert size < MAX_BYTES, size
 
 
 if __name__ == "__main__":

@@ -9,7 +9,18 @@ T1  ``StockMVSNet(float64)`` -- ``dmvsnet_amd.train.wire``, the function ``DiffM
     2000 roundings, i.e. about 2e-13 in float64 (measured: 4.8e-13); 1e-9 is four decades above that and seven below what a wrong
     ``detach``, a FeatureNet run on the B * V batch or one flipped ReLU produces.  In float64 against float64 no decision flips.
     The mutation tests show that the comparison sees each of those.
-T2  every rule of ``DiffMVSNet`` raises a ``DmvsError`` that names it, on CPU tensors included; the state-dict keys are the stock
+    The same on the axes of the reference's training recipe (scripts/train.sh: ``--inverse_depth``, ``--ndepths 48 32 8``,
+    ``--num_view 5``, ``--batch_size 2``), one fixture per case of ``train_step_ref.FIXTURES``: ``b2_32x32_inv`` (inverse-depth sampling)
+    and ``b2_32x32_recipe`` (all four flags) in train mode as above; ``b2_32x32_unlike`` -- every sample its own reference camera and
+    depth range -- in EVAL mode against the reference run once per sample with B = 1: with such a batch the reference takes sample 0's
+    intervals for every sample's planes and ``wire`` does not (dmvsnet_amd/train.py, "One deviation"), so in train mode the two differ
+    by 0.28 in a stage-1 output; on running statistics the samples are independent and every sample of the batch must be its own run.
+    There the comparison is per sample: the differentiable outputs and the hypothesis volume of every sample, the two confidences of
+    sample 0, and those of sample b > 0 against the reference's lines on its own ``depth_sub_plus`` with sample 0's ``interval`` (the
+    documented rule); the gradients against the sum of the per-sample runs'.  Five more mutations -- ``inverse`` dropped in either
+    hypothesis builder, planes or projections of sample 0 for every sample, the interval of another sample -- are seen by these cases
+    and by no other.
+T2 every rule of ``DiffMVSNet`` raises a ``DmvsError`` that names it, on CPU tensors included; the state-dict keys are the stock
     model's and ``dmvsnet_amd.MVSNet``'s; T5's graph-edge assertions on the stock model (the GPU test runs the same function on
     ``DiffMVSNet``).
 """
@@ -28,18 +39,37 @@ CASE = "b2_32x32"
 
 
 @pytest.fixture(scope="module")
-def fixture(golden):
-    return golden("op_train_step.npz")
+def fixtures(golden):
+    cache = {}
+    return lambda name: cache[name] if name in cache else cache.setdefault(name, golden(T.FIXTURES[name]))
 
 
 @pytest.fixture(scope="module")
-def case():
-    kw = T.CASES[CASE]
-    return dict(kw=kw, inputs=T.make_inputs(**kw), weights=T.functional_weights(**kw), sd=T.make_state_dict(kw["seed"]))
+def cases():
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            kw = T.CASES[name]
+            cache[name] = dict(name=name, kw=kw, inputs=T.make_inputs(**kw), weights=T.functional_weights(**kw),
+                               sd=T.make_state_dict(kw["seed"]))
+        return cache[name]
+    return get
+
+
+@pytest.fixture(scope="module")
+def fixture(fixtures):
+    return fixtures(CASE)
+
+
+@pytest.fixture(scope="module")
+def case(cases):
+    return cases(CASE)
 
 
 def _step(case, mutate=None):
-    net = T.stock_model(case["sd"], torch.float64)
+    """One forward + backward of the case's stock float64 model: train mode, the unlike case in eval mode (as its fixture)."""
+    net = T.stock_of(case["name"], case["sd"], torch.float64, train_mode=not case["kw"].get("unlike", False))
     if mutate is not None:
         mutate(net)
     outs, grads, _ = T.run_step(net, case["inputs"], lambda o: T.linear_functional(o, case["weights"]))
@@ -47,13 +77,26 @@ def _step(case, mutate=None):
 
 
 def _distances(fixture, net, outs, grads):
-    """{stored key: distance to the stored array}, normalised by the stored tensor's max-abs (digests: see below)."""
+    """{stored key: distance to the stored array}, normalised by the stored tensor's max-abs (digests: see below).  A fixture of
+    per-sample runs (it stores ``itv.*``) is compared per sample: the key gets the sample's index."""
     dist = {}
     buffers = T.bn_buffers(net)
+    per_sample = any(k.startswith("itv.") for k in fixture)
     for key in fixture:
         kind, _, name = key.partition(".")
         want = torch.from_numpy(np.asarray(fixture[key]))
-        if kind == "out":
+        if kind == "out" and per_sample:
+            stage, _, what = name.partition(".")
+            for b in range(want.shape[0]):
+                w = want[b]
+                if "confidence" in what and b > 0:   # the documented rule: sample 0's interval on the sample's own depth_sub_plus
+                    dsp = fixture[f"out.{stage}." + ("depth_sub_plus_refine" if what.endswith("refine") else "depth_sub_plus")]
+                    w = T.confidence(torch.from_numpy(dsp[b:b + 1]), torch.tensor(fixture[f"itv.{stage}"][0], dtype=torch.float64))[0]
+                dist[f"{key}[{b}]"] = T.rel_dist(outs[stage][what][b], w)
+        elif kind == "itv":   # what the reference's own run of sample 0 reports, and another number for every other sample
+            dist[key] = abs(float(outs[name]["interval"]) - float(want[0])) / float(want[0])
+            assert all(float(w) != float(want[0]) for w in want[1:])
+        elif kind == "out":
             stage, _, what = name.partition(".")
             dist[key] = T.rel_dist(outs[stage][what], want)
         elif kind == "buf":
@@ -70,38 +113,101 @@ def _distances(fixture, net, outs, grads):
     return dist
 
 
-def test_fixture_holds_what_the_test_needs(fixture, case):
+def test_fixture_holds_what_the_test_needs(fixtures, case):
     params = [n for n, _ in T.stock_model(case["sd"], torch.float64).named_parameters()]
     assert len(params) == 403
-    assert {k[7:] for k in fixture if k.startswith("digest.")} == set(params)
-    assert sum(k.startswith("buf.") and k.endswith("num_batches_tracked") for k in fixture) == 8 + 12 * 10
-    assert sum(k.startswith("grad.") and ".bn." in k for k in fixture) == 2 * (8 + 12 * 10)
-    assert sum(k.startswith("grad.") and k.endswith("prob.weight") for k in fixture) == 12
-    assert sum(k.startswith("out.") for k in fixture) == 3 * (len(T.STAGE_OUTPUTS) - 1)
-    assert all(np.asarray(fixture[k]).dtype == np.float64 for k in fixture if k.startswith(("out.", "grad.", "digest.")))
+    for name in T.FIXTURES:
+        fixture, kw = fixtures(name), T.CASES[name]
+        assert {k[7:] for k in fixture if k.startswith("digest.")} == set(params), name
+        assert all(np.asarray(fixture[k]).dtype == np.float64 for k in fixture if k.startswith(("out.", "grad.", "digest.", "itv."))), name
+        assert ("descent.losses" in fixture) == (name == CASE)
+        if kw.get("unlike"):   # per-sample runs in eval mode: every stage output of every sample, the intervals, the digests
+            assert {k.partition(".")[0] for k in fixture} == {"out", "itv", "digest", "fp32"}
+            assert sum(k.startswith("out.") for k in fixture) == 3 * len(T.STAGE_OUTPUTS)
+            assert all(fixture[k].shape[0] == kw["B"] for k in fixture if k.startswith(("out.", "itv.")))
+            continue
+        assert sum(k.startswith("buf.") and k.endswith("num_batches_tracked") for k in fixture) == 8 + 12 * 10, name
+        assert sum(k.startswith("grad.") and ".bn." in k for k in fixture) == 2 * (8 + 12 * 10), name
+        assert sum(k.startswith("grad.") and k.endswith("prob.weight") for k in fixture) == 12, name
+        assert sum(k.startswith("out.") for k in fixture) == 3 * (len(T.STAGE_OUTPUTS) - 1), name
 
 
-def test_wiring_reproduces_the_reference_in_float64(fixture, case):
-    net, outs, grads = _step(case)
-    dist = _distances(fixture, net, outs, grads)
-    assert len(dist) == sum(not k.startswith(("fp32.", "descent.")) for k in fixture)
-    worst = max(dist, key=dist.get)
-    print(f"TRAINSTEP T1: {len(dist)} stored quantities, largest distance {dist[worst]:.2e} ({worst}); the reference's own fp32 run: outputs "
-          f"{fixture['fp32.out'].max():.2e}, gradients median {np.median(fixture['fp32.grad']):.2e} max {fixture['fp32.grad'].max():.2e}")
-    bad = {k: v for k, v in dist.items() if not v <= TOL}
+def test_unlike_inputs_are_unlike():
+    """What the unlike cases are made of: sample 1 is sample 0's image set no more, its reference camera is camera 1 with its image,
+    and its depth range has another start and another step, the ground truth's surface inside both."""
+    kw = T.CASES["b2_32x32_unlike"]
+    like, unlike = T.make_inputs(**{**kw, "unlike": False}), T.make_inputs(**kw)
+    assert all(torch.equal(a[0], b[0]) for a, b in zip(like[:1] + like[2:], unlike[:1] + unlike[2:]))   # sample 0 as it was
+    order = T.view_order(1, kw["V"])
+    assert order[0] == 1 and sorted(order) == list(range(kw["V"]))
+    assert torch.equal(unlike[0][1], like[0][1, order]) and not torch.equal(unlike[0][1], like[0][1])
+    for key in like[1]:
+        assert torch.equal(unlike[1][key][0], like[1][key][0]) and torch.equal(unlike[1][key][1], like[1][key][1, order])
+        assert not torch.equal(unlike[1][key][1, 0, 0], unlike[1][key][0, 0, 0])   # another reference camera
+    dv = unlike[2]
+    assert float(dv[1, 0]) != float(dv[0, 0]) and abs(float(dv[1, 1] - dv[1, 0]) / float(dv[0, 1] - dv[0, 0]) - 1) > 0.1
+    gt, _ = T.make_ground_truth(**kw)
+    assert all(float(dv[b, 0]) < float(g[b].min()) and float(g[b].max()) < float(dv[b, -1]) for g in gt.values() for b in range(kw["B"]))
+
+
+def test_wiring_reproduces_the_reference_in_float64(fixtures, cases):
+    bad = {}
+    for name in T.FIXTURES:
+        fixture, case = fixtures(name), cases(name)
+        net, outs, grads = _step(case)
+        dist = _distances(fixture, net, outs, grads)
+        B = case["kw"]["B"] if case["kw"].get("unlike") else 1   # a fixture of per-sample runs: every output once per sample
+        assert len(dist) == sum((B if k.startswith("out.") else 1) for k in fixture if not k.startswith(("fp32.", "descent.")))
+        worst = max(dist, key=dist.get)
+        print(f"TRAINSTEP T1 {name}: {len(dist)} stored quantities, largest distance {dist[worst]:.2e} ({worst}); the reference's own fp32 "
+              f"run: outputs {fixture['fp32.out'].max():.2e}, gradients median {np.median(fixture['fp32.grad']):.2e} max "
+              f"{fixture['fp32.grad'].max():.2e}")
+        bad.update({(name, k): v for k, v in dist.items() if not v <= TOL})
+        tracked = {k: int(v) for k, v in T.bn_buffers(net).items() if k.endswith("num_batches_tracked")}
+        if case["kw"].get("unlike"):   # eval mode updates nothing
+            assert all(v == 0 for v in tracked.values())
+        else:   # FeatureNet ran once per view: V updates of its BatchNorms, one of every other
+            assert all(v == (case["kw"]["V"] if k.startswith("feature.") else 1) for k, v in tracked.items())
     assert not bad, bad
-    # FeatureNet ran once per view: V = 3 updates of its BatchNorms, one of every other
-    tracked = {k: int(v) for k, v in T.bn_buffers(net).items() if k.endswith("num_batches_tracked")}
-    assert all(v == (3 if k.startswith("feature.") else 1) for k, v in tracked.items())
 
 
-@pytest.mark.parametrize("mutation", ["detach_depth_values_c", "flip_one_relu", "batched_featurenet"])
-def test_the_comparison_sees_a_wrong_graph(fixture, case, mutation, monkeypatch):
-    """What 1e-9 is seven decades below: each mutation of the wiring moves a stored quantity by far more than the bound."""
+def _other_sample(parts, mutation):
+    """The mutations that only a batch of unlike samples can see, on the namespace ``wire`` is about to run."""
+    first, later, agg = parts.hypotheses_first, parts.hypotheses_next, parts.cost_agg
+    if mutation == "planes_of_sample_0":
+        parts.hypotheses_first = lambda dv, *a: first(dv[:1].expand_as(dv), *a)
+        parts.hypotheses_next = lambda last, dv, *a: later(last, dv[:1].expand_as(dv), *a)
+    elif mutation == "projections_of_sample_0":
+        parts.cost_agg = lambda feats, proj, hyp: agg(feats, proj[:1].expand_as(proj).contiguous(), hyp)
+    elif mutation == "interval_of_last_sample":
+        parts.hypotheses_first = lambda dv, *a: (first(dv, *a)[0], first(dv.flip(0), *a)[1])
+        parts.hypotheses_next = lambda last, dv, *a: (later(last, dv, *a)[0], later(last.flip(0), dv.flip(0), *a)[1])
+
+
+MUTATIONS = {"detach_depth_values_c": CASE, "flip_one_relu": CASE, "batched_featurenet": CASE,
+             "inverse_dropped_next": "b2_32x32_inv", "inverse_dropped_first": "b2_32x32_inv",
+             "planes_of_sample_0": "b2_32x32_unlike", "projections_of_sample_0": "b2_32x32_unlike",
+             "interval_of_last_sample": "b2_32x32_unlike"}
+
+
+@pytest.mark.parametrize("mutation", list(MUTATIONS))
+def test_the_comparison_sees_a_wrong_graph(fixtures, cases, mutation, monkeypatch):
+    """What 1e-9 is seven decades below: each mutation of the wiring moves a stored quantity by far more than the bound.  The last
+    five are seen by the inverse-depth and unlike cases only: on the first case (linear sampling, like samples) each of them computes
+    the same bits as the unmutated wiring, which the test shows too."""
+    fixture, case = fixtures(MUTATIONS[mutation]), cases(MUTATIONS[mutation])
     real_wire = train.wire
 
     def wire(parts, imgs, *args, **kw):
-        if mutation == "detach_depth_values_c":
+        if mutation == "inverse_dropped_next":
+            real_next = parts.hypotheses_next
+            parts.hypotheses_next = lambda last, dv, ratio, D, inverse: real_next(last, dv, ratio, D, False)
+        elif mutation == "inverse_dropped_first":
+            real_first = parts.hypotheses_first
+            parts.hypotheses_first = lambda dv, D, h, w, inverse: real_first(dv, D, h, w, False)
+        elif mutation in ("planes_of_sample_0", "projections_of_sample_0", "interval_of_last_sample"):
+            _other_sample(parts, mutation)
+        elif mutation == "detach_depth_values_c":
             real_head = parts.head
             parts.head = lambda *a: {k: (v.detach() if k == "depth_values_c" else v) for k, v in real_head(*a).items()}
         elif mutation == "batched_featurenet":
@@ -129,8 +235,16 @@ def test_the_comparison_sees_a_wrong_graph(fixture, case, mutation, monkeypatch)
     net, outs, grads = _step(case, mutate)
     dist = _distances(fixture, net, outs, grads)
     worst = max(dist, key=dist.get)
-    print(f"TRAINSTEP T1 mutation {mutation}: largest distance {dist[worst]:.2e} ({worst})")
+    print(f"TRAINSTEP T1 mutation {mutation} on {case['name']}: largest distance {dist[worst]:.2e} ({worst}), {dist[worst] / TOL:.1e} "
+          f"times the bound; largest over the stage outputs alone {max(v for k, v in dist.items() if k.startswith('out.')):.2e}")
     assert dist[worst] > 1e4 * TOL
+    if MUTATIONS[mutation] != CASE:   # ... and the first case cannot see it: the same bits with and without
+        first = cases(CASE)
+        with torch.no_grad():
+            mutated = T.stock_of(CASE, first["sd"], torch.float64)(*first["inputs"])
+            monkeypatch.setattr(train, "wire", real_wire)
+            plain = T.stock_of(CASE, first["sd"], torch.float64)(*first["inputs"])
+        assert all(torch.equal(mutated[f"stage{s + 1}"][k], plain[f"stage{s + 1}"][k]) for s in range(3) for k in T.STAGE_OUTPUTS + ("interval",))
 
 
 def test_fp32_cost_aggregation_is_the_float64_helper_with_a_dtype():
@@ -180,10 +294,11 @@ def graph_edges(model, inputs, loss_of_outputs):
             assert something(grads, "feature.out1.") and something(grads, "feature.conv0.")
 
 
-def test_graph_edges_of_the_stock_model(case):
-    kw = case["kw"]
-    gt, mask = T.make_ground_truth(**kw)
-    graph_edges(T.stock_model(case["sd"], torch.float64), case["inputs"], lambda o: T.stock_loss(o, gt, mask))
+def test_graph_edges_of_the_stock_model(cases):
+    for name in (CASE, "b2_32x32_inv"):   # linear and inverse-depth sampling
+        case = cases(name)
+        gt, mask = T.make_ground_truth(**case["kw"])
+        graph_edges(T.stock_of(name, case["sd"], torch.float64), case["inputs"], lambda o: T.stock_loss(o, gt, mask))
 
 
 # ------------------------------------------------------------------------------------------------ T2

@@ -2,8 +2,9 @@
 ``dmvsnet_amd.train.wire`` over stock ATen parts on the CPU, and ``ForcedDecisions``.  No product kernel runs here.
 
 ``StockMVSNet(float64)`` is the yardstick, ``StockMVSNet(float32)`` the ``e_ref`` arm.  tests/test_train_step_cpu.py holds the float64
-form to a float64 run of the reference's own ``MVSNet`` (tests/golden/op_train_step.npz) to 1e-9: that certifies the wiring function and
-this file together; everything on the GPU is then held to this file.
+form to float64 runs of the reference's own ``MVSNet`` (tests/golden/op_train_step*.npz, one per case of ``FIXTURES``: linear and inverse
+depth, the training recipe's planes and views, a batch of unlike samples) to 1e-9: that certifies the wiring function and this file
+together; everything on the GPU is then held to this file.
 
 The parts, from the helpers that exist:
 
@@ -48,10 +49,22 @@ DLOSSW = (0.5, 1.0, 2.0)   # the reference's recipe (scripts/train.sh)
 GROUPS = ("feature",) + tuple(f"{net}.{s}" for net in ("cost_regularization", "cost_regularization_refine") for s in range(3))
 DIFF_OUTPUTS = ("depth_sub_plus", "depth_values_c", "depth_sub_plus_refine", "depth")
 STAGE_OUTPUTS = DIFF_OUTPUTS + ("depth_values", "photometric_confidence", "photometric_confidence_refine")
-# the cases: T1 (CPU, against the reference), T3 / T4 first case, T3 second case
+RECIPE = (48, 32, 8)       # --ndepths of the recipe; with it go --inverse_depth, --num_view 5, --batch_size 2
+# the cases: T1 (CPU, against the reference), T3 / T4 first case, T3 second case; then the recipe's axes.  ``inverse``: inverse-depth
+# sampling; ``unlike``: every sample its own reference camera and depth range (``make_inputs``).  *_32x32_*: CPU, against the reference
+# (one fixture each, ``FIXTURES``); the others: GPU, against ``StockMVSNet``.
 CASES = {"b2_32x32": dict(B=2, V=3, H=32, W=32, ndepths=NDEPTHS, seed=0),
          "b2_32x64": dict(B=2, V=3, H=32, W=64, ndepths=NDEPTHS, seed=0),
-         "b1_64x96": dict(B=1, V=3, H=64, W=96, ndepths=(48, 32, 8), seed=0)}
+         "b1_64x96": dict(B=1, V=3, H=64, W=96, ndepths=RECIPE, seed=0),
+         "b2_32x32_inv": dict(B=2, V=3, H=32, W=32, ndepths=NDEPTHS, seed=0, inverse=True),
+         "b2_32x32_recipe": dict(B=2, V=5, H=32, W=32, ndepths=RECIPE, seed=0, inverse=True),
+         "b2_32x32_unlike": dict(B=2, V=3, H=32, W=32, ndepths=NDEPTHS, seed=0, inverse=True, unlike=True),
+         "b2_32x64_inv": dict(B=2, V=3, H=32, W=64, ndepths=NDEPTHS, seed=0, inverse=True),
+         "b2_64x96_recipe": dict(B=2, V=5, H=64, W=96, ndepths=RECIPE, seed=0, inverse=True),
+         "b2_32x64_unlike": dict(B=2, V=3, H=32, W=64, ndepths=NDEPTHS, seed=0, inverse=True, unlike=True)}
+FIXTURES = {"b2_32x32": "op_train_step.npz", "b2_32x32_inv": "op_train_step_inv.npz", "b2_32x32_recipe": "op_train_step_recipe.npz",
+            "b2_32x32_unlike": "op_train_step_unlike.npz"}
+GT_RANGE = (640.0 - 90.0 - 5.0, 640.0 + 90.0 + 5.0)   # make_ground_truth's surface: 640 +- (50 + 40) mm and five sigma of its noise
 
 
 def group_of(name):
@@ -59,12 +72,29 @@ def group_of(name):
 
 
 # ------------------------------------------------------------------------------------------------ inputs
-def make_inputs(B, V, H, W, seed=0, **_):
+def view_order(b, V):
+    """The order in which sample ``b`` of an unlike batch takes the V synth views: rotated by b, so its reference view is camera b."""
+    return [(v + b) % V for v in range(V)]
+
+
+def make_inputs(B, V, H, W, seed=0, unlike=False, **_):
     """imgs [B,V,3,H,W] (another image set per sample), proj_matrices {"stageK": [B,V,2,4,4]}, depth_values [B,192]: the samples
-    share the cameras and the depth range.  fp32, CPU."""
+    share the cameras and the depth range.  fp32, CPU.  ``unlike``: sample b > 0 takes its views (images and cameras together) in
+    ``view_order(b, V)`` and its own depth range, 425 + 70 b + (2.65 / (1 + b)) i: another ``depth_min`` AND another interval, with
+    ``make_ground_truth``'s surface inside every sample's range (asserted)."""
     imgs = torch.cat([synth.synth_images(H, W, V, seed=seed + 1000 * b) for b in range(B)])
     proj = {k: v.repeat(B, 1, 1, 1, 1) for k, v in synth.synth_cameras(H, W, V).items()}
-    return imgs, proj, synth.synth_depth_values().repeat(B, 1)
+    dv = synth.synth_depth_values().repeat(B, 1)
+    if unlike:
+        for b in range(1, B):
+            order = view_order(b, V)
+            imgs[b] = imgs[b, order]
+            for k in proj:
+                proj[k][b] = proj[k][b, order]
+            dv[b] = torch.from_numpy(np.float32(425.0 + 70.0 * b) + np.float32(2.65 / (1 + b)) * np.arange(dv.shape[1], dtype=np.float32))
+        assert all(float(dv[b, 0]) <= GT_RANGE[0] and float(dv[b, -1]) >= GT_RANGE[1] for b in range(B)), "the surface leaves a depth range"
+        assert all(float(dv[b, 0]) != float(dv[0, 0]) and float(dv[b, 1] - dv[b, 0]) != float(dv[0, 1] - dv[0, 0]) for b in range(1, B))
+    return imgs, proj, dv
 
 
 def make_state_dict(seed=0):
@@ -173,7 +203,7 @@ class _Head(torch.autograd.Function):
         return g_logits, g_hyp, None, None, None
 
 
-def _confidence(dsp, interval):
+def confidence(dsp, interval):
     with torch.no_grad():   # networks/mvsnet.py:59-62
         return 2 * (torch.sigmoid(interval / (dsp.var(1, unbiased=False).sqrt() + 1e-5)) - 0.5)
 
@@ -204,12 +234,12 @@ class StockMVSNet(nn.Module):
 
         def head(cost_reg, hyp, interval):
             dsp, c = _Head.apply(cost_reg, hyp, 1.0, 0, route("main"))
-            return {"photometric_confidence": _confidence(dsp, interval), "depth_sub_plus": dsp, "depth_values_c": c, "depth_values": hyp,
+            return {"photometric_confidence": confidence(dsp, interval), "depth_sub_plus": dsp, "depth_values_c": c, "depth_values": hyp,
                     "interval": interval}
 
         def head_refine(cost_reg, hyp_c, interval):
             dsp, depth = _Head.apply(cost_reg, hyp_c, HG.REFINE_ALPHA, 1, route("refine"))
-            return {"depth": depth, "photometric_confidence_refine": _confidence(dsp, interval), "depth_sub_plus_refine": dsp}
+            return {"depth": depth, "photometric_confidence_refine": confidence(dsp, interval), "depth_sub_plus_refine": dsp}
 
         def hypotheses_first(depth_values, D, h, w, inverse):
             per = [HY.first(dv, D, h, w, inverse, dt) for dv in depth_values]
@@ -230,8 +260,8 @@ class StockMVSNet(nn.Module):
                           self.inverse_depth)
 
 
-def stock_model(sd, dtype, ndepths=NDEPTHS, ratios=RATIOS, train_mode=True):
-    net = StockMVSNet(ndepths, ratios, torch.float32)
+def stock_model(sd, dtype, ndepths=NDEPTHS, ratios=RATIOS, train_mode=True, inverse_depth=False):
+    net = StockMVSNet(ndepths, ratios, torch.float32, inverse_depth)
     net.load_state_dict(sd, strict=True)
     net = net.to(dtype)
     net.dtype = dtype
@@ -326,6 +356,12 @@ def run_step(model, inputs, loss_fn, forced=None, record=None):
     loss = loss_fn(outputs)
     loss.backward()
     return outputs, {n: p.grad for n, p in model.named_parameters()}, loss.detach()
+
+
+def stock_of(name, sd, dtype, train_mode=True):
+    """``stock_model`` of a case of the table: its ``ndepths`` and ``inverse``."""
+    kw = CASES[name]
+    return stock_model(sd, dtype, kw["ndepths"], train_mode=train_mode, inverse_depth=kw.get("inverse", False))
 
 
 def bn_buffers(model):
