@@ -54,11 +54,13 @@ FeatureNet's conv1.0 / conv2.0 (networks/module.py:289, :295).  Even and odd H, 
   no transposed 5x5 form, and nothing is packed or cached for this direction;
 * weight gradient: K3k (``ops.conv2d_k5s2_wgrad``), accumulated over the samples in batch order.
 
-In the code: one autograd Function (``_ConvFn``) runs every kind of layer; a ``_Kind`` value per kind (square, stride-2, transposed, ends,
-5x5) names the builder of its packed layers (the gather and the ``ConvLayer``), the forms of the weight the forward and the data gradient
-launch, the ``ops.conv3d`` backend, the weight-gradient call with its argument order and, for the 5x5 kind, the data-gradient call that
-stands in for the ``ops.conv3d`` launch.  Every packed layer comes through one cache
-lookup (``_cached_layer``; ``_packed_layer*`` name it per kind), and the four classes share their constructor and ``forward``
+In the code: one autograd Function (``_ConvFn``) runs every kind of layer, FeatureNet's rectangular ones included
+(``dmvsnet_amd.featurenet``: the sixth kind, which brings the optional bias and conv0.0's launch on its 3-channel sample in place).  A
+``_Kind`` value per kind (square, stride-2, transposed, ends, 5x5, rectangular) names the builder of its packed layers (the family's
+gather index, ``ops.gather_packed`` and the ``ConvLayer``), the forms of the weight the forward and the data gradient launch, the
+``ops.conv3d`` backend, the weight-gradient call with its argument order and, for the 5x5 kind, the data-gradient call that stands in
+for the ``ops.conv3d`` launch.  Every packed layer comes through one cache lookup (``_cached_layer``; ``_biased_layer`` keys a
+lateral's on its bias too; ``_packed_layer*`` name it per kind), and the four classes share their constructor and ``forward``
 (``_DiffConv``, mixed in front of the nn class).
 """
 from __future__ import annotations
@@ -98,30 +100,42 @@ def _cached_layer(cache: dict, slot, weight: torch.Tensor, build, kdepth: int) -
     return layer
 
 
+def _biased_layer(cache: dict, weight: torch.Tensor, bias: torch.Tensor, kind: "_Kind", kdepth: int) -> ops.ConvLayer:
+    """The layer of the forward launch of a layer with a ``bias``: its epilogue adds the bias, and the slot also carries the bias's data
+    pointer and device."""
+    slot = (kind.fwd, bias.data_ptr(), bias.device)
+    for old in [k for k in cache if isinstance(k, tuple) and k != slot]:   # (a bias that moved leaves no layer behind)
+        del cache[old]
+    return _cached_layer(cache, slot, weight, lambda w, kd, s: kind.build(w, kd, kind.fwd, bias), kdepth)
+
+
+# The builders: (weight, kdepth, the form of the weight) -> the bare layer (no scale / shift / ReLU), packed on the device by one gather
 def _build_s1(weight, kdepth, transposed_flipped):
     C = weight.shape[0]
-    index = ops.pack_index_mfma(C, kdepth, transposed_flipped, weight.device)
-    packed = torch.index_select(weight.detach().reshape(-1), 0, index)   # one device gather: the packing is a permutation
+    packed = ops.gather_packed(weight, ops.pack_index_mfma(C, kdepth, transposed_flipped, weight.device), False)
     return ops.ConvLayer("diffconv%d%s" % (C, "t" if transposed_flipped else ""), ops.CONV_S1, kdepth, C, C, None, packed, None, None, False)
 
 
 def _build_s2(weight, kdepth, mode):
     big, small = weight.shape[0], weight.shape[1]
     cin, cout = (small, big) if mode == ops.CONV_S2 else (big, small)
-    index = ops.pack_index_mfma_s2(cin, cout, mode, kdepth, weight.device)
-    flat = weight.detach().reshape(-1)
-    packed = torch.index_select(torch.cat((flat, flat.new_zeros(1))), 0, index)   # a selection with zeros: the appended slot is the zero
+    packed = ops.gather_packed(weight, ops.pack_index_mfma_s2(cin, cout, mode, kdepth, weight.device), True)
     return ops.ConvLayer("diff%s%dto%d" % ("conv_s2_" if mode == ops.CONV_S2 else "deconv_s2_", cin, cout), mode, kdepth, cin, cout, None,
                          packed, None, None, False)
 
 
 def _build_c2(weight, kdepth, transposed_flipped):
     cout, cin = weight.shape[0], weight.shape[1]
-    index = ops.pack_index_direct(cin, cout, transposed_flipped, weight.device)
-    packed = torch.index_select(weight.detach().reshape(-1), 0, index)   # one device gather: the packing is a permutation
+    packed = ops.gather_packed(weight, ops.pack_index_direct(cin, cout, transposed_flipped, weight.device), False)
     lin, lout = (cout, cin) if transposed_flipped else (cin, cout)
     return ops.ConvLayer("diffconv%dto%d%s" % (cin, cout, "t" if transposed_flipped else ""), ops.CONV_S1, 3, lin, lout, packed, None, None,
                          None, False)
+
+
+def _build_k5(weight, kdepth, slot):
+    cout, cin = weight.shape[0], weight.shape[1]
+    packed = ops.gather_packed(weight, ops.pack_index_mfma_k5s2(cin, cout, weight.device), True)
+    return ops.ConvLayer("diffconv_k5s2_%dto%d" % (cin, cout), ops.CONV2D_K5S2, 1, cin, cout, None, packed, None, None, False)
 
 
 def _packed_layer(cache: dict, weight: torch.Tensor, kdepth: int, transposed_flipped: bool) -> ops.ConvLayer:
@@ -141,20 +155,13 @@ def _packed_layer_c2(cache: dict, weight: torch.Tensor, transposed_flipped: bool
     return _cached_layer(cache, transposed_flipped, weight, _build_c2, 3)
 
 
+# The weight-gradient calls in the Function's argument order (x, gy, kdepth, out=, accumulate=)
 def _wgrad_down(x, gy, kdepth, **kw):
     return ops.conv3d_wgrad_s2(gy, x, kdepth, **kw)   # K3h takes (coarse, fine)
 
 
 def _wgrad_ends(x, gy, kdepth, **kw):
     return ops.conv3d_wgrad_c2(x, gy, **kw)
-
-
-def _build_k5(weight, kdepth, slot):
-    cout, cin = weight.shape[0], weight.shape[1]
-    index = ops.pack_index_mfma_k5s2(cin, cout, weight.device)
-    flat = weight.detach().reshape(-1)
-    packed = torch.index_select(torch.cat((flat, flat.new_zeros(1))), 0, index)   # a selection with zeros, as _build_s2
-    return ops.ConvLayer("diffconv_k5s2_%dto%d" % (cin, cout), ops.CONV2D_K5S2, 1, cin, cout, None, packed, None, None, False)
 
 
 def _wgrad_k5(x, gy, kdepth, **kw):
@@ -167,7 +174,7 @@ def _dgrad_k5(gy, weight, x, out):
 
 @dataclass(frozen=True)
 class _Kind:
-    """What tells the five kinds of layer apart behind _ConvFn."""
+    """What tells the kinds of layer apart behind _ConvFn."""
     build: Callable          # the builder of its packed layers (_cached_layer)
     fwd: Union[bool, int]    # the form of the weight the forward launches: the builder's last argument and the cache slot
     bwd: Union[bool, int]    # ... and the data gradient
@@ -185,30 +192,46 @@ _UP = _Kind(_build_s2, ops.DECONV_S2, ops.CONV_S2, "mfma", ops.conv3d_wgrad_s2)
 _ENDS = _Kind(_build_c2, False, True, "direct", _wgrad_ends)
 # FeatureNet's 5x5 stride-2 layers: K3's CONV2D_K5S2 forward; no K3 launch has the data gradient's shape, K3d has it on the raw weight
 _DOWN5 = _Kind(_build_k5, ops.CONV2D_K5S2, None, "mfma", _wgrad_k5, _dgrad_k5)
+# (the sixth kind, FeatureNet's rectangular stride-1 layers, is dmvsnet_amd.featurenet._FPN)
 
 
 class _ConvFn(torch.autograd.Function):
+    """x [B,Cin,D,H,W], or [B,Cin,H,W] of a 2D layer (its samples run as D = 1 volumes: the axis is inserted and removed here, on
+    detached tensors), weight, the module's cache of packed layers, the kind; ``bias`` [Cout] (the two FeatureNet laterals only: the
+    kind's builder and its weight-gradient call take it) -> [B,Cout,D',H',W'] resp. [B,Cout,H',W']."""
+
     @staticmethod
-    def forward(ctx, x, weight, cache, kind):
+    def forward(ctx, x, weight, cache, kind, bias=None):
         xd = x.detach()
-        kdepth = 3 if weight.dim() == 5 else 1   # (a 2D layer's samples come as D = 1 volumes)
-        layer = _cached_layer(cache, kind.fwd, weight, kind.build, kdepth)
+        flat = xd.dim() == 4
+        if flat:
+            xd = xd.unsqueeze(2)
+        kdepth = 3 if weight.dim() == 5 else 1
+        if bias is None:
+            layer = _cached_layer(cache, kind.fwd, weight, kind.build, kdepth)
+        else:
+            layer = _biased_layer(cache, weight, bias, kind, kdepth)
         if layer.mode == ops.CONV_S1 and layer.cout == layer.cin:   # a square layer: the output has the input's shape
             out = torch.empty_like(xd)
         else:
             out = xd.new_empty((xd.shape[0], layer.cout, *layer.out_shape(*xd.shape[2:])))
         for b in range(xd.shape[0]):
-            ops.conv3d(xd[b], layer, out=out[b], backend=kind.backend)
-        ctx.save_for_backward(xd, weight)
-        ctx.kdepth, ctx.cache, ctx.kind = kdepth, cache, kind
-        return out
+            if layer.cin == 4:   # FeatureNet's conv0.0, K3's 4-channel layer: the sample as a stack of one 3-channel view, read in place
+                ops.conv3d(xd[b:b + 1].squeeze(2), layer, out=out[b], backend=kind.backend, in_views=True)
+            else:
+                ops.conv3d(xd[b], layer, out=out[b], backend=kind.backend)
+        ctx.save_for_backward(xd, weight, *(() if bias is None else (bias,)))
+        ctx.kdepth, ctx.cache, ctx.kind, ctx.flat = kdepth, cache, kind, flat
+        return out.squeeze(2) if flat else out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        x, weight = ctx.saved_tensors   # (raises if the weight was changed in place since the forward)
+        x, weight, *bias = ctx.saved_tensors   # (raises if the weight or the bias was changed in place since the forward)
         gy = gy.contiguous()
-        gx = gw = None
+        if ctx.flat:
+            gy = gy.unsqueeze(2)
+        gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
             if ctx.kind.dgrad is None:
@@ -219,12 +242,20 @@ class _ConvFn(torch.autograd.Function):
                 else:
                     ctx.kind.dgrad(gy[b], weight.detach(), x[b], gx[b])
                 launch_counts["dgrad"] += 1
-        if ctx.needs_input_grad[1]:
+        with_bias = {}
+        if bias and ctx.needs_input_grad[4]:   # (the bias alone needs the weight-gradient kernel too: one launch pair gives both)
+            gb = torch.empty_like(bias[0])
+            with_bias = {"bias_out": gb}
+        if ctx.needs_input_grad[1] or gb is not None:
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
             for b in range(x.shape[0]):
-                ctx.kind.wgrad(x[b], gy[b], ctx.kdepth, out=gw, accumulate=b > 0)
+                ctx.kind.wgrad(x[b], gy[b], ctx.kdepth, out=gw, accumulate=b > 0, **with_bias)
                 launch_counts["wgrad"] += 1
-        return gx, gw, None, None
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        if gx is not None and ctx.flat:
+            gx = gx.squeeze(2)
+        return gx, gw, None, None, gb
 
 
 def _check_even(what, x, nd):
@@ -311,9 +342,7 @@ class _DiffConv:
         if down:
             _check_even(what, x, nd)
         with torch.cuda.device(x.device):
-            if nd == 3:
-                return _ConvFn.apply(x, weight, self._packed, kind)
-            return _ConvFn.apply(x.unsqueeze(2), weight, self._packed, kind).squeeze(2)
+            return _ConvFn.apply(x, weight, self._packed, kind)
 
 
 class _DiffConvTranspose(_DiffConv):

@@ -29,6 +29,8 @@ square layers and the 5x5 stride-2 layers stay there).
 Autograd keeps the input, the weight and the bias.  Packed layers are cached per module as in ``dmvsnet_amd.conv`` (``_cached_layer``:
 keyed on the weight's version counter, data pointer and device; the laterals' key also carries the bias's data pointer and device).
 fp32, contiguous, on a HIP device, any H, W.  No atomics: forward and gradients are bitwise reproducible.  Double backward raises.
+In the code the layers are one more ``_Kind`` (``_FPN``) behind ``dmvsnet_amd.conv._ConvFn``, each sample a D = 1 volume: this module
+holds the kind's builder and weight-gradient call, the constructor's refusals and the refusals of ``forward``.
 
 ``DiffFeatureConvBlock2d`` is the reference's ``Conv2d`` block (:28) on ``DiffFeatureConv2d`` + ``DiffBatchNormReLU2d`` (K5), for
 conv0.0 / conv0.1; children and state-dict keys are the reference's.
@@ -46,12 +48,11 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 from torch import nn
-from torch.autograd.function import once_differentiable
 
 from . import ops
 from ._lib import DmvsError
 from .bn import DiffBatchNormReLU2d, DiffConvBlock2d, _DiffBlock
-from .conv import DiffConv2d, _cached_layer, _check_input, _check_weight, _Kind, launch_counts
+from .conv import DiffConv2d, _check_input, _check_weight, _ConvFn, _Kind
 
 __all__ = ["DiffFeatureConv2d", "DiffFeatureConvBlock2d", "DiffFeatureNet", "SHAPES", "BIAS_SHAPES"]
 
@@ -63,9 +64,7 @@ def _build_fpn(weight, kdepth, transposed_flipped, bias=None):
     """The bare K3 layer of ``weight`` [out,in,k,k] (with ``bias``: its epilogue adds the bias) or of its transposed-flipped form, the
     layer out -> in of the data gradient."""
     cout, cin, k = (int(n) for n in weight.shape[:3])
-    index = ops.pack_index_mfma_fpn(cin, cout, k, transposed_flipped, weight.device)
-    flat = weight.detach().reshape(-1)
-    packed = torch.index_select(torch.cat((flat, flat.new_zeros(1))), 0, index)   # a selection with zeros: the appended slot is the zero
+    packed = ops.gather_packed(weight, ops.pack_index_mfma_fpn(cin, cout, k, transposed_flipped, weight.device), True)
     lin, lout = (cout, cin) if transposed_flipped else (max(cin, 4), cout)        # (conv0.0: K3's 4-channel layer)
     scale = shift = None
     if bias is not None:
@@ -81,59 +80,8 @@ def _wgrad_fpn(x, gy, kdepth, **kw):
     return ops.conv2d_wgrad_fpn(x, gy, _KERNEL[(int(x.shape[0]), int(gy.shape[0]))], **kw)
 
 
-# FeatureNet's rectangular stride-1 layers: K3 forward, K3 on the transposed-flipped weight for the data gradient, K3f
+# FeatureNet's rectangular stride-1 layers behind conv._ConvFn: K3 forward, K3 on the transposed-flipped weight for the data gradient, K3f
 _FPN = _Kind(_build_fpn, False, True, "mfma", _wgrad_fpn)
-
-
-def _forward_layer(cache, weight, bias, kind):
-    if bias is None:
-        return _cached_layer(cache, kind.fwd, weight, kind.build, 1)
-    slot = (kind.fwd, bias.data_ptr(), bias.device)
-    for old in [k for k in cache if isinstance(k, tuple) and k != slot]:   # (a bias that moved leaves no layer behind)
-        del cache[old]
-    return _cached_layer(cache, slot, weight, lambda w, kd, s: kind.build(w, kd, kind.fwd, bias), 1)
-
-
-class _FeatureConvFn(torch.autograd.Function):
-    """x [B,Cin,H,W], weight [Cout,Cin,k,k], bias [Cout] or None -> [B,Cout,H,W]; each sample is a D = 1 volume."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, cache, kind):
-        xd = x.detach()
-        layer = _forward_layer(cache, weight, bias, kind)
-        out = xd.new_empty((xd.shape[0], layer.cout, *xd.shape[2:]))
-        for b in range(xd.shape[0]):
-            if layer.cin == 4:   # conv0.0: the sample as a stack of one 3-channel view, read in place
-                ops.conv3d(xd[b:b + 1], layer, out=out[b].unsqueeze(1), backend=kind.backend, in_views=True)
-            else:
-                ops.conv3d(xd[b].unsqueeze(1), layer, out=out[b].unsqueeze(1), backend=kind.backend)
-        ctx.save_for_backward(xd, weight, *(() if bias is None else (bias,)))
-        ctx.cache, ctx.kind, ctx.has_bias = cache, kind, bias is not None
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors[:2]   # (raises if the weight or the bias was changed in place since the forward)
-        gy = gy.contiguous()
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            layer = _cached_layer(ctx.cache, ctx.kind.bwd, weight, ctx.kind.build, 1)
-            for b in range(x.shape[0]):
-                ops.conv3d(gy[b].unsqueeze(1), layer, out=gx[b].unsqueeze(1), backend=ctx.kind.backend)
-                launch_counts["dgrad"] += 1
-        need_gb = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or need_gb:
-            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-            if need_gb:
-                gb = torch.empty_like(ctx.saved_tensors[2])
-            for b in range(x.shape[0]):
-                ctx.kind.wgrad(x[b].unsqueeze(1), gy[b].unsqueeze(1), 1, out=gw, bias_out=gb, accumulate=b > 0)
-                launch_counts["wgrad"] += 1
-            if not ctx.needs_input_grad[1]:
-                gw = None
-        return gx, gw, gb, None, None
 
 
 def _check_ctor(what, m):
@@ -163,8 +111,8 @@ class DiffFeatureConv2d(nn.Conv2d):
             raise DmvsError(f"{what}: the bias must be contiguous fp32 on the input's device {x.device}; it is {bias.dtype} on {bias.device}")
         if self.in_channels == 3 and x.requires_grad:
             raise DmvsError(f"{what}: conv0.0 has no data gradient (the image takes none); the input must not require one")
-        with torch.cuda.device(x.device):
-            return _FeatureConvFn.apply(x, weight, bias, self._packed, _FPN)
+        with torch.cuda.device(x.device):   # (each sample a D = 1 volume, as DiffConv2d's)
+            return _ConvFn.apply(x, weight, self._packed, _FPN, bias)
 
 
 class DiffFeatureConvBlock2d(_DiffBlock):

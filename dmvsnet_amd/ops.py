@@ -6,13 +6,15 @@ in the product (the CPU restatement lives in oracle/ and is test infrastructure)
 
 Every launch that is logged and timed goes through ``_launch``: it checks the devices of the weights, hands the timer's start event
 back when the launch fails, and writes the launch log and the timer record.  The training wrappers share one workspace cache
-(``_workspace``; the four public getters query their size and delegate), one gather-index cache (``_pack_index``; the three
-``pack_index_*`` functions supply the builder).  The three weight-gradient wrappers keep a body each: one body would take eleven
-parameters.
+(``_workspace``) and one gather-index cache (``_pack_index``); the five ``pack_index_*`` functions share one derivation
+(``_derive_index``) and the layers one gather (``gather_packed``).  The five weight-gradient wrappers keep a body each -- its shape
+rule, output shape, argument tuple, cost and launch -- around one frame: ``_wgrad_out`` (the buffer) and ``_wgrad_workspace`` (which
+the five public getters call too).
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence
 
@@ -907,7 +909,7 @@ def dual_depth_loss_backward(dsp_main: torch.Tensor, dsp_refine: torch.Tensor, g
     return g_main, g_refine
 
 
-# ------------------------------------------------------------------------------------------ training: shared by K3g / K3h / K2g / K5
+# ------------------------------------------------------------------------------------------ training: shared by K3g / K3h / K2g / K3k / K3f / K5
 _pack_index_cache: dict = {}
 _ws_cache: dict = {}
 
@@ -927,6 +929,46 @@ def _pack_index(key: tuple, build: Callable[[], torch.Tensor], device) -> torch.
     return idx
 
 
+def _transposed_flipped(w: torch.Tensor) -> torch.Tensor:
+    """``w`` transposed in (co, ci) and flipped in every tap: the weight of a stride-1 layer's data gradient."""
+    return w.transpose(0, 1).flip(tuple(range(2, w.dim())))
+
+
+def _derive_index(what: str, shape, arrange: Optional[Callable], pack: Callable, permutation: bool) -> torch.Tensor:
+    """The one derivation behind the five pack_index_* functions (``what``: the one that asks).  For a weight of ``shape`` with n
+    elements: ``pack(arrange(iota + 1))`` -- the iota in the weight's layout, re-arranged as the layer's weight is (``arrange`` None: as
+    it lies), through the library's packer -- minus 1 is the element every packed slot selects; a zero of the packed form selects the
+    slot n, which the gather appends (gather_packed).  Every element must be selected exactly once; with ``permutation`` the slot n must
+    not be selected at all, so the index serves ``w.reshape(-1)[index]`` as it is."""
+    n = 1
+    for k in shape:
+        n *= int(k)
+    if n < 1 or n + 1 >= (1 << 24):   # iota + 1 travels as fp32
+        raise _lib.DmvsError(f"{what}: a weight {tuple(shape)} has no gather index (1 <= elements < 2^24 - 1)")
+    iota = (torch.arange(n, dtype=torch.float32) + 1.0).reshape(*shape)
+    packed = pack(iota if arrange is None else arrange(iota).contiguous())
+    if packed is None:
+        raise _lib.DmvsError(f"{what}: the library does not compile the layer of a weight {tuple(shape)}")
+    idx = packed.reshape(-1).to(torch.int64) - 1
+    idx[idx < 0] = n
+    counts = torch.bincount(idx, minlength=n + 1)
+    if not torch.equal(counts[:n], torch.ones(n, dtype=torch.int64)):
+        raise _lib.DmvsError(f"{what}: the packing of a weight {tuple(shape)} does not select every weight element exactly once")
+    if permutation and int(counts[n]):
+        raise _lib.DmvsError(f"{what}: the packing of a weight {tuple(shape)} is not a permutation")
+    return idx
+
+
+def gather_packed(weight: torch.Tensor, index: torch.Tensor, zero_slot: bool) -> torch.Tensor:
+    """The packed form of ``weight`` by one device gather through its pack_index_* ``index``.  ``zero_slot``: the family's packings
+    are selections with zeros, which select the one zero appended here; the permutation families (pack_index_mfma, pack_index_direct)
+    gather the weight as it lies."""
+    flat = weight.detach().reshape(-1)
+    if zero_slot:
+        flat = torch.cat((flat, flat.new_zeros(1)))
+    return torch.index_select(flat, 0, index)
+
+
 def _workspace(kind: str, n: int, device) -> torch.Tensor:
     """The cached workspace of ``n`` floats of the kernel family ``kind``, one per (kind, size, device, stream)."""
     dev = torch.device(device)
@@ -939,6 +981,35 @@ def _workspace(kind: str, n: int, device) -> torch.Tensor:
     return ws
 
 
+def _no_buffer(what: str) -> _lib.DmvsError:
+    return _lib.DmvsError(f"{what}: accumulate needs the buffer to add to (out)")
+
+
+def _wgrad_out(what: str, out: Optional[torch.Tensor], accumulate: bool, shape: tuple, x: torch.Tensor) -> torch.Tensor:
+    """The buffer the weight-gradient wrapper ``what`` writes a gradient of ``shape`` into: ``out``, or a new one beside ``x``."""
+    if out is None:
+        if accumulate:
+            raise _no_buffer(what)
+        return torch.empty(shape, dtype=torch.float32, device=x.device)
+    if out.numel() != math.prod(shape):
+        raise _lib.DmvsError(f"{what}: out {tuple(out.shape)} is not a [{','.join(map(str, shape))}] weight")
+    return out
+
+
+def _wgrad_workspace(what: str, kind: str, n: int, dims: tuple, device, workspace: Optional[torch.Tensor] = None,
+                     kernel: str = "weight-gradient kernel") -> torch.Tensor:
+    """The workspace of the weight-gradient wrapper ``what``, ``n`` = the library's size for ``dims`` (the arguments of
+    dmvs_<what>_workspace; <= 0: the kernel does not cover them): ``workspace`` if it is large enough, else the cached buffer of the
+    family ``kind``, one per (size, device, stream) -- the sizes do not depend on the volume."""
+    if workspace is None:
+        if n <= 0:
+            raise _lib.DmvsError(f"{what}: the shape {tuple(dims)} (as dmvs_{what}_workspace takes it) is not covered by the {kernel}")
+        return _workspace(kind, n, device)
+    if workspace.numel() < n:
+        raise _lib.DmvsError(f"{what}: workspace too small ({workspace.numel()} floats, {n} needed)")
+    return workspace
+
+
 # ------------------------------------------------------------------------------------------ K3g (training: the stride-1 square convs)
 WGRAD_TILE = (1, 4, 32)   # voxel tile (z, y, x) of K3g: dmvs_conv3d_wgrad_plan counts these (csrc/conv3d_wgrad.h)
 
@@ -948,30 +1019,19 @@ def pack_index_mfma(C: int, kdepth: int, transposed_flipped: bool, device=None) 
     C -> C: for a weight ``w`` in nn.Conv3d / nn.Conv2d layout ``w.reshape(-1)[index] == pack_mfma(w, C, C, CONV_S1, kdepth)`` bit for
     bit (the packing of these shapes is a pure permutation).  ``transposed_flipped``: the index of
     ``pack_mfma(w.transpose(0, 1).flip(2, 3, 4), ...)`` instead -- the weight of the layer's data gradient.  Derived once on the host
-    by packing an iota through the library's packer."""
+    by packing an iota through the library's packer (_derive_index)."""
     def build():
-        n = C * C * 9 * kdepth
-        if kdepth not in (1, 3) or n >= (1 << 24):   # the iota travels as fp32
+        if kdepth not in (1, 3):
             raise _lib.DmvsError(f"pack_index_mfma: C = {C}, kdepth = {kdepth}")
-        iota = torch.arange(n, dtype=torch.float32).reshape(C, C, kdepth, 3, 3)
-        if transposed_flipped:
-            iota = iota.transpose(0, 1).flip(2, 3, 4).contiguous()
-        packed = pack_mfma(iota, C, C, CONV_S1, kdepth)
-        if packed is None:
-            raise _lib.DmvsError(f"pack_index_mfma: K3 does not compile the stride-1 layer {C} -> {C}, kdepth {kdepth}")
-        idx = packed.to(torch.int64)
-        if idx.numel() != n or not torch.equal(torch.sort(idx).values, torch.arange(n)):
-            raise _lib.DmvsError(f"pack_index_mfma: the packing of {C} -> {C}, kdepth {kdepth} is not a permutation")
-        return idx
+        return _derive_index("pack_index_mfma", (C, C, kdepth, 3, 3), _transposed_flipped if transposed_flipped else None,
+                             lambda w: pack_mfma(w, C, C, CONV_S1, kdepth), True)
     return _pack_index((int(C), int(kdepth), bool(transposed_flipped)), build, device)
 
 
 def conv3d_wgrad_workspace(C: int, D: int, H: int, W: int, kdepth: int, device) -> torch.Tensor:
     """K3g's workspace, one per (shape class, device, stream): its size does not depend on the volume."""
-    n = _lib.load().dmvs_conv3d_wgrad_workspace(C, D, H, W, kdepth)
-    if n <= 0:
-        raise _lib.DmvsError(f"conv3d_wgrad: C = {C}, kdepth = {kdepth}, volume {(D, H, W)} is not covered by the weight-gradient kernel")
-    return _workspace("k3g", n, device)
+    dims = (C, D, H, W, kdepth)
+    return _wgrad_workspace("conv3d_wgrad", "k3g", _lib.load().dmvs_conv3d_wgrad_workspace(*dims), dims, device)
 
 
 def conv3d_wgrad(x: torch.Tensor, gy: torch.Tensor, kdepth: int, out: Optional[torch.Tensor] = None, accumulate: bool = False,
@@ -983,20 +1043,11 @@ def conv3d_wgrad(x: torch.Tensor, gy: torch.Tensor, kdepth: int, out: Optional[t
     if x.dim() != 4 or x.shape != gy.shape:
         raise _lib.DmvsError(f"conv3d_wgrad: x {tuple(x.shape)} and gy {tuple(gy.shape)} must be the same [C,D,H,W]")
     C, D, H, W = x.shape
-    if accumulate and out is None:
-        raise _lib.DmvsError("conv3d_wgrad: accumulate needs the buffer to add to (out)")
-    if out is None:
-        out = torch.empty((C, C, kdepth, 3, 3), dtype=torch.float32, device=x.device)
-    elif out.numel() != C * C * kdepth * 9:
-        raise _lib.DmvsError(f"conv3d_wgrad: out {tuple(out.shape)} is not a [{C},{C},{kdepth},3,3] weight")
-    if workspace is None:
-        workspace = conv3d_wgrad_workspace(C, D, H, W, kdepth, x.device)
-    elif workspace.numel() < _lib.load().dmvs_conv3d_wgrad_workspace(C, D, H, W, kdepth):
-        raise _lib.DmvsError("conv3d_wgrad: workspace too small")
-    cost = None
-    if timer is not None:
-        cost = (2.0 * 9 * kdepth * C * C * D * H * W, 4.0 * (2 * C * D * H * W + 9 * kdepth * C * C), None)
-    _launch(_lib.load().dmvs_conv3d_wgrad, (_ptr(x), _ptr(gy), _ptr(out), _ptr(workspace), C, D, H, W, kdepth, 1 if accumulate else 0),
+    lib, dims = _lib.load(), (C, D, H, W, kdepth)
+    out = _wgrad_out("conv3d_wgrad", out, accumulate, (C, C, kdepth, 3, 3), x)
+    workspace = _wgrad_workspace("conv3d_wgrad", "k3g", lib.dmvs_conv3d_wgrad_workspace(*dims), dims, x.device, workspace)
+    cost = None if timer is None else (2.0 * 9 * kdepth * C * C * D * H * W, 4.0 * (2 * C * D * H * W + 9 * kdepth * C * C), None)
+    _launch(lib.dmvs_conv3d_wgrad, (_ptr(x), _ptr(gy), _ptr(out), _ptr(workspace), *dims, 1 if accumulate else 0),
             f"wgrad{C}k{kdepth}", "wgrad", x, (gy, out, workspace), False, "conv3d_wgrad", cost)
     _log("conv3d_wgrad")   # two dispatches per call: the partials and their sum (scripts/pmc_summary.py joins by dispatch order)
     return out
@@ -1011,15 +1062,13 @@ def pack_index_direct(cin: int, cout: int, transposed_flipped: bool, device=None
     """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K2's weight packing for a 3x3x3 layer
     cin -> cout: for a weight ``w`` [cout,cin,3,3,3] ``w.reshape(-1)[index] == pack_direct(w, False).reshape(-1)`` bit for bit (the
     packing is a pure permutation).  ``transposed_flipped``: the index of ``pack_direct(w.transpose(0, 1).flip(2, 3, 4), False)``
-    instead -- the weight of the layer's data gradient, a cout -> cin layer.  Derived once on the host by packing an iota."""
+    instead -- the weight of the layer's data gradient, a cout -> cin layer.  Derived once on the host by packing an iota
+    (_derive_index)."""
     def build():
-        n = cin * cout * 27
-        if cin < 1 or cout < 1 or n >= (1 << 24):   # the iota travels as fp32
+        if cin < 1 or cout < 1:
             raise _lib.DmvsError(f"pack_index_direct: cin = {cin}, cout = {cout}")
-        iota = torch.arange(n, dtype=torch.float32).reshape(cout, cin, 3, 3, 3)
-        if transposed_flipped:
-            iota = iota.transpose(0, 1).flip(2, 3, 4).contiguous()
-        return pack_direct(iota, False).reshape(-1).to(torch.int64)
+        return _derive_index("pack_index_direct", (cout, cin, 3, 3, 3), _transposed_flipped if transposed_flipped else None,
+                             lambda w: pack_direct(w, False), True)
     return _pack_index(("direct", int(cin), int(cout), bool(transposed_flipped)), build, device)
 
 
@@ -1032,10 +1081,8 @@ def _wgrad_c2_dims(x: torch.Tensor, gy: torch.Tensor):
 
 def conv3d_wgrad_c2_workspace(Cin: int, Cout: int, D: int, H: int, W: int, device) -> torch.Tensor:
     """K2g's workspace, one per (size, device, stream): its size does not depend on the volume."""
-    n = _lib.load().dmvs_conv3d_wgrad_c2_workspace(Cin, Cout, D, H, W)
-    if n <= 0:
-        raise _lib.DmvsError(f"conv3d_wgrad_c2: (Cin, Cout) = {(Cin, Cout)}, volume {(D, H, W)} is not covered by the weight-gradient kernel")
-    return _workspace("k2g", n, device)
+    dims = (Cin, Cout, D, H, W)
+    return _wgrad_workspace("conv3d_wgrad_c2", "k2g", _lib.load().dmvs_conv3d_wgrad_c2_workspace(*dims), dims, device)
 
 
 def conv3d_wgrad_c2(x: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False,
@@ -1045,21 +1092,12 @@ def conv3d_wgrad_c2(x: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Tenso
     result is ADDED to it (it must then be given).  ``workspace``: at least dmvs_conv3d_wgrad_c2_workspace floats (default: a cached
     buffer per device and stream)."""
     _req(x, gy, out, workspace)
-    Cin, Cout, D, H, W = _wgrad_c2_dims(x, gy)
-    if accumulate and out is None:
-        raise _lib.DmvsError("conv3d_wgrad_c2: accumulate needs the buffer to add to (out)")
-    if out is None:
-        out = torch.empty((Cout, Cin, 3, 3, 3), dtype=torch.float32, device=x.device)
-    elif out.numel() != Cout * Cin * 27:
-        raise _lib.DmvsError(f"conv3d_wgrad_c2: out {tuple(out.shape)} is not a [{Cout},{Cin},3,3,3] weight")
-    if workspace is None:
-        workspace = conv3d_wgrad_c2_workspace(Cin, Cout, D, H, W, x.device)
-    elif workspace.numel() < _lib.load().dmvs_conv3d_wgrad_c2_workspace(Cin, Cout, D, H, W):
-        raise _lib.DmvsError("conv3d_wgrad_c2: workspace too small")
-    cost = None
-    if timer is not None:
-        cost = (2.0 * 27 * Cin * Cout * D * H * W, 4.0 * ((Cin + Cout) * D * H * W + 27 * Cin * Cout), None)
-    _launch(_lib.load().dmvs_conv3d_wgrad_c2, (_ptr(x), _ptr(gy), _ptr(out), _ptr(workspace), Cin, Cout, D, H, W, 1 if accumulate else 0),
+    Cin, Cout, D, H, W = dims = _wgrad_c2_dims(x, gy)
+    lib = _lib.load()
+    out = _wgrad_out("conv3d_wgrad_c2", out, accumulate, (Cout, Cin, 3, 3, 3), x)
+    workspace = _wgrad_workspace("conv3d_wgrad_c2", "k2g", lib.dmvs_conv3d_wgrad_c2_workspace(*dims), dims, x.device, workspace)
+    cost = None if timer is None else (2.0 * 27 * Cin * Cout * D * H * W, 4.0 * ((Cin + Cout) * D * H * W + 27 * Cin * Cout), None)
+    _launch(lib.dmvs_conv3d_wgrad_c2, (_ptr(x), _ptr(gy), _ptr(out), _ptr(workspace), *dims, 1 if accumulate else 0),
             f"wgrad{Cin}to{Cout}", "wgrad_c2", x, (gy, out, workspace), False, "conv3d_wgrad_c2", cost)
     _log("conv3d_wgrad_c2")   # two dispatches per call: the partials and their sum (scripts/pmc_summary.py joins by dispatch order)
     return out
@@ -1073,26 +1111,16 @@ WGRAD_S2_TILE = {(16, 3): (1, 4, 32), (32, 3): (1, 4, 32), (64, 3): (1, 2, 32), 
 def pack_index_mfma_s2(cin: int, cout: int, mode: int, kdepth: int, device=None) -> torch.Tensor:
     """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K3's weight packing for a stride-2 layer
     (``mode`` CONV_S2, weight [cout][cin][k..]) or a transposed one (DECONV_S2, weight [cin][cout][k..]) with cout = 2 cin resp.
-    cin = 2 cout: ``torch.cat((w.reshape(-1), zeros(1)))[index] == pack_mfma(w, cin, cout, mode, kdepth)`` bit for bit.  These
-    packings are selections with zeros, not permutations (conv1's packed-K form pads its last k-step, conv11's y-parity-merged form has
-    zero rows): a zero of the packed form selects the one appended zero slot, index n = cin * cout * 9 * kdepth.  Derived once on the
-    host by packing ``iota + 1`` through the library's packer; every weight element must be selected exactly once."""
+    cin = 2 cout: ``gather_packed(w, index, True) == pack_mfma(w, cin, cout, mode, kdepth)`` bit for bit.  These packings are
+    selections with zeros, not permutations (conv1's packed-K form pads its last k-step, conv11's y-parity-merged form has zero rows):
+    a zero of the packed form selects the one appended zero slot, index n = cin * cout * 9 * kdepth.  Derived once on the host by
+    packing ``iota + 1`` through the library's packer (_derive_index); every weight element must be selected exactly once."""
     def build():
-        n = cin * cout * 9 * kdepth
         ok = (mode == CONV_S2 and cout == 2 * cin) or (mode == DECONV_S2 and cin == 2 * cout)
-        if not ok or kdepth not in (1, 3) or n < 1 or n + 1 >= (1 << 24):   # the iota travels as fp32
+        if not ok or kdepth not in (1, 3):
             raise _lib.DmvsError(f"pack_index_mfma_s2: {cin} -> {cout}, mode {mode}, kdepth {kdepth} is no stride-2 or transposed layer")
         lead = (cout, cin) if mode == CONV_S2 else (cin, cout)
-        iota = (torch.arange(n, dtype=torch.float32) + 1.0).reshape(*lead, kdepth, 3, 3)
-        packed = pack_mfma(iota, cin, cout, mode, kdepth)
-        if packed is None:
-            raise _lib.DmvsError(f"pack_index_mfma_s2: K3 does not compile the layer {cin} -> {cout}, mode {mode}, kdepth {kdepth}")
-        idx = packed.to(torch.int64) - 1
-        idx[idx < 0] = n
-        if not torch.equal(torch.bincount(idx, minlength=n + 1)[:n], torch.ones(n, dtype=torch.int64)):
-            raise _lib.DmvsError(f"pack_index_mfma_s2: the packing of {cin} -> {cout}, mode {mode}, kdepth {kdepth} does not select every "
-                                 "weight element exactly once")
-        return idx
+        return _derive_index("pack_index_mfma_s2", (*lead, kdepth, 3, 3), None, lambda w: pack_mfma(w, cin, cout, mode, kdepth), False)
     return _pack_index(("s2", int(cin), int(cout), int(mode), int(kdepth)), build, device)
 
 
@@ -1109,11 +1137,9 @@ def _wgrad_s2_dims(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int):
 
 def conv3d_wgrad_s2_workspace(Ca: int, Dc: int, Hc: int, Wc: int, kdepth: int, device) -> torch.Tensor:
     """K3h's workspace, one per (shape class, device, stream): its size does not depend on the volume."""
-    n = _lib.load().dmvs_conv3d_wgrad_s2_workspace(Ca, Dc, Hc, Wc, kdepth)
-    if n <= 0:
-        raise _lib.DmvsError(f"conv3d_wgrad_s2: Ca = {Ca}, kdepth = {kdepth}, coarse volume {(Dc, Hc, Wc)} is not covered by the strided "
-                             "weight-gradient kernel")
-    return _workspace("k3h", n, device)
+    dims = (Ca, Dc, Hc, Wc, kdepth)
+    return _wgrad_workspace("conv3d_wgrad_s2", "k3h", _lib.load().dmvs_conv3d_wgrad_s2_workspace(*dims), dims, device,
+                            kernel="strided weight-gradient kernel")
 
 
 def conv3d_wgrad_s2(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int, out: Optional[torch.Tensor] = None, accumulate: bool = False,
@@ -1125,22 +1151,15 @@ def conv3d_wgrad_s2(coarse: torch.Tensor, fine: torch.Tensor, kdepth: int, out: 
     ``workspace``: at least dmvs_conv3d_wgrad_s2_workspace floats (default: a cached buffer per device and stream)."""
     _req(coarse, fine, out, workspace)
     Ca, Dc, Hc, Wc = _wgrad_s2_dims(coarse, fine, kdepth)
-    if accumulate and out is None:
-        raise _lib.DmvsError("conv3d_wgrad_s2: accumulate needs the buffer to add to (out)")
-    if out is None:
-        out = torch.empty((Ca, Ca // 2, kdepth, 3, 3), dtype=torch.float32, device=coarse.device)
-    elif out.numel() != Ca * (Ca // 2) * kdepth * 9:
-        raise _lib.DmvsError(f"conv3d_wgrad_s2: out {tuple(out.shape)} is not a [{Ca},{Ca // 2},{kdepth},3,3] weight")
-    if workspace is None:
-        workspace = conv3d_wgrad_s2_workspace(Ca, Dc, Hc, Wc, kdepth, coarse.device)
-    elif workspace.numel() < _lib.load().dmvs_conv3d_wgrad_s2_workspace(Ca, Dc, Hc, Wc, kdepth):
-        raise _lib.DmvsError("conv3d_wgrad_s2: workspace too small")
+    lib, dims = _lib.load(), (Ca, Dc, Hc, Wc, kdepth)
+    out = _wgrad_out("conv3d_wgrad_s2", out, accumulate, (Ca, Ca // 2, kdepth, 3, 3), coarse)
+    workspace = _wgrad_workspace("conv3d_wgrad_s2", "k3h", lib.dmvs_conv3d_wgrad_s2_workspace(*dims), dims, coarse.device, workspace,
+                                 "strided weight-gradient kernel")
     cost = None
     if timer is not None:
         nt = 9 * kdepth * Ca * (Ca // 2)
         cost = (2.0 * nt * Dc * Hc * Wc, 4.0 * (coarse.numel() + fine.numel() + nt), None)
-    _launch(_lib.load().dmvs_conv3d_wgrad_s2,
-            (_ptr(coarse), _ptr(fine), _ptr(out), _ptr(workspace), Ca, Dc, Hc, Wc, kdepth, 1 if accumulate else 0),
+    _launch(lib.dmvs_conv3d_wgrad_s2, (_ptr(coarse), _ptr(fine), _ptr(out), _ptr(workspace), *dims, 1 if accumulate else 0),
             f"wgrad_s2_{Ca}k{kdepth}", "wgrad_s2", coarse, (fine, out, workspace), False, "conv3d_wgrad_s2", cost)
     _log("conv3d_wgrad_s2")   # two dispatches per call: the partials and their sum
     return out
@@ -1153,23 +1172,14 @@ WGRAD_K5S2_SHAPES = ((8, 16), (16, 32))  # (Cin, Cout): conv1.0 and conv2.0
 
 def pack_index_mfma_k5s2(cin: int, cout: int, device=None) -> torch.Tensor:
     """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K3's weight packing for a 5x5 stride-2 layer
-    (CONV2D_K5S2, weight [cout][cin][5][5], cout = 2 cin): ``torch.cat((w.reshape(-1), zeros(1)))[index] ==
-    pack_mfma(w, cin, cout, CONV2D_K5S2, 1)`` bit for bit.  A zero of the packed form (conv1.0's packed-K form may pad) selects the one
-    appended zero slot, index n = cin * cout * 25.  Derived once on the host by packing ``iota + 1`` through the library's packer;
-    every weight element must be selected exactly once."""
+    (CONV2D_K5S2, weight [cout][cin][5][5], cout = 2 cin): ``gather_packed(w, index, True) == pack_mfma(w, cin, cout, CONV2D_K5S2, 1)``
+    bit for bit.  A zero of the packed form (conv1.0's packed-K form may pad) selects the one appended zero slot, index
+    n = cin * cout * 25.  Derived once on the host by packing ``iota + 1`` through the library's packer (_derive_index); every weight
+    element must be selected exactly once."""
     def build():
-        n = cin * cout * 25
         if (cin, cout) not in WGRAD_K5S2_SHAPES:
             raise _lib.DmvsError(f"pack_index_mfma_k5s2: {cin} -> {cout} is no 5x5 stride-2 layer of FeatureNet {WGRAD_K5S2_SHAPES}")
-        iota = (torch.arange(n, dtype=torch.float32) + 1.0).reshape(cout, cin, 5, 5)   # (n + 1 < 2^24: the iota travels as fp32)
-        packed = pack_mfma(iota, cin, cout, CONV2D_K5S2, 1)
-        if packed is None:
-            raise _lib.DmvsError(f"pack_index_mfma_k5s2: K3 does not compile the 5x5 stride-2 layer {cin} -> {cout}")
-        idx = packed.to(torch.int64) - 1
-        idx[idx < 0] = n
-        if not torch.equal(torch.bincount(idx, minlength=n + 1)[:n], torch.ones(n, dtype=torch.int64)):
-            raise _lib.DmvsError(f"pack_index_mfma_k5s2: the packing of {cin} -> {cout} does not select every weight element exactly once")
-        return idx
+        return _derive_index("pack_index_mfma_k5s2", (cout, cin, 5, 5), None, lambda w: pack_mfma(w, cin, cout, CONV2D_K5S2, 1), False)
     return _pack_index(("k5s2", int(cin), int(cout)), build, device)
 
 
@@ -1187,11 +1197,9 @@ def _k5s2_dims(what: str, gy: torch.Tensor, fine_shape):
 
 def conv2d_k5s2_wgrad_workspace(Ca: int, D: int, Hf: int, Wf: int, device) -> torch.Tensor:
     """K3k's workspace, one per (shape class, device, stream): its size does not depend on the image."""
-    n = _lib.load().dmvs_conv2d_k5s2_wgrad_workspace(Ca, D, Hf, Wf)
-    if n <= 0:
-        raise _lib.DmvsError(f"conv2d_k5s2_wgrad: Ca = {Ca}, planes {D}, image {(Hf, Wf)} is not covered by the 5x5 stride-2 "
-                             "weight-gradient kernel")
-    return _workspace("k3k", n, device)
+    dims = (Ca, D, Hf, Wf)
+    return _wgrad_workspace("conv2d_k5s2_wgrad", "k3k", _lib.load().dmvs_conv2d_k5s2_wgrad_workspace(*dims), dims, device,
+                            kernel="5x5 stride-2 weight-gradient kernel")
 
 
 def conv2d_k5s2_wgrad(x: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False,
@@ -1202,22 +1210,16 @@ def conv2d_k5s2_wgrad(x: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Ten
     to it (it must then be given).  ``workspace``: at least dmvs_conv2d_k5s2_wgrad_workspace floats (default: a cached buffer per device
     and stream)."""
     _req(x, gy, out, workspace)
-    Ca, D, Hf, Wf = _k5s2_dims("conv2d_k5s2_wgrad", gy, x.shape)
-    if accumulate and out is None:
-        raise _lib.DmvsError("conv2d_k5s2_wgrad: accumulate needs the buffer to add to (out)")
-    if out is None:
-        out = torch.empty((Ca, Ca // 2, 5, 5), dtype=torch.float32, device=x.device)
-    elif out.numel() != Ca * (Ca // 2) * 25:
-        raise _lib.DmvsError(f"conv2d_k5s2_wgrad: out {tuple(out.shape)} is not a [{Ca},{Ca // 2},5,5] weight")
-    if workspace is None:
-        workspace = conv2d_k5s2_wgrad_workspace(Ca, D, Hf, Wf, x.device)
-    elif workspace.numel() < _lib.load().dmvs_conv2d_k5s2_wgrad_workspace(Ca, D, Hf, Wf):
-        raise _lib.DmvsError("conv2d_k5s2_wgrad: workspace too small")
+    Ca, D, Hf, Wf = dims = _k5s2_dims("conv2d_k5s2_wgrad", gy, x.shape)
+    lib = _lib.load()
+    out = _wgrad_out("conv2d_k5s2_wgrad", out, accumulate, (Ca, Ca // 2, 5, 5), x)
+    workspace = _wgrad_workspace("conv2d_k5s2_wgrad", "k3k", lib.dmvs_conv2d_k5s2_wgrad_workspace(*dims), dims, x.device, workspace,
+                                 "5x5 stride-2 weight-gradient kernel")
     cost = None
     if timer is not None:
         nt = 25 * Ca * (Ca // 2)
         cost = (2.0 * nt * D * gy.shape[2] * gy.shape[3], 4.0 * (gy.numel() + x.numel() + nt), None)
-    _launch(_lib.load().dmvs_conv2d_k5s2_wgrad, (_ptr(gy), _ptr(x), _ptr(out), _ptr(workspace), Ca, D, Hf, Wf, 1 if accumulate else 0),
+    _launch(lib.dmvs_conv2d_k5s2_wgrad, (_ptr(gy), _ptr(x), _ptr(out), _ptr(workspace), *dims, 1 if accumulate else 0),   # (coarse, fine)
             f"wgrad_k5s2_{Ca}", "wgrad_k5s2", x, (gy, out, workspace), False, "conv2d_k5s2_wgrad", cost)
     _log("conv2d_k5s2_wgrad")   # two dispatches per call: the partials and their sum
     return out
@@ -1255,33 +1257,26 @@ FPN_BIAS_SHAPES = ((16, 32, 1), (8, 32, 1))   # ... of which these two have a bi
 
 def pack_index_mfma_fpn(cin: int, cout: int, ksize: int, transposed_flipped: bool, device=None) -> torch.Tensor:
     """Gather index (cached LongTensor; on the CPU, or a cached copy on ``device``) of K3's weight packing for the layer
-    ``(cin, cout, ksize)`` of FPN_SHAPES, weight ``w`` [cout,cin,ksize,ksize]: ``torch.cat((w.reshape(-1), zeros(1)))[index]`` equals,
+    ``(cin, cout, ksize)`` of FPN_SHAPES, weight ``w`` [cout,cin,ksize,ksize]: ``gather_packed(w, index, True)`` equals,
     bit for bit, ``pack_mfma(w, cin, cout, mode, 1)`` with mode CONV_S1 (kernel 3) or CONV2D_K1 (kernel 1) -- for cin = 3 the packing of
     ``w`` with a zero fourth channel, as make_layer packs conv0.0.  ``transposed_flipped``: the index of
     ``pack_mfma(w.transpose(0, 1).flip(2, 3), cout, cin, mode, 1)`` instead -- the weight of the layer's data gradient, a layer
     cout -> cin (conv0.0 has none: the image takes no gradient).  These packings are selections with zeros (the zero channel, the zero
     rows of 8 output channels on the 16-row MFMA): a zero selects the one appended slot, index n = cin * cout * ksize^2.  Derived once
-    on the host by packing ``iota + 1`` through the library's packer; every weight element must be selected exactly once."""
+    on the host by packing ``iota + 1`` through the library's packer (_derive_index); every weight element must be selected exactly
+    once."""
     def build():
         if (cin, cout, ksize) not in FPN_SHAPES or (transposed_flipped and cin == 3):
             raise _lib.DmvsError(f"pack_index_mfma_fpn: ({cin}, {cout}, {ksize}), transposed_flipped = {transposed_flipped} is no layer "
                                  f"of FeatureNet's head {FPN_SHAPES} (conv0.0 has no data gradient)")
-        n = cin * cout * ksize * ksize
-        iota = (torch.arange(n, dtype=torch.float32) + 1.0).reshape(cout, cin, ksize, ksize)   # (n + 1 < 2^24: the iota travels as fp32)
-        lin, lout = cin, cout
-        if transposed_flipped:
-            iota, lin, lout = iota.transpose(0, 1).flip(2, 3).contiguous(), cout, cin
-        if lin == 3:
-            iota, lin = torch.cat((iota, torch.zeros_like(iota[:, :1])), 1).contiguous(), 4
-        packed = pack_mfma(iota, lin, lout, CONV_S1 if ksize == 3 else CONV2D_K1, 1)
-        if packed is None:
-            raise _lib.DmvsError(f"pack_index_mfma_fpn: K3 does not compile the layer {lin} -> {lout}, kernel {ksize}")
-        idx = packed.to(torch.int64) - 1
-        idx[idx < 0] = n
-        if not torch.equal(torch.bincount(idx, minlength=n + 1)[:n], torch.ones(n, dtype=torch.int64)):
-            raise _lib.DmvsError(f"pack_index_mfma_fpn: the packing of {lin} -> {lout}, kernel {ksize} does not select every weight "
-                                 "element exactly once")
-        return idx
+        lin, lout = (cout, cin) if transposed_flipped else (max(cin, 4), cout)   # (conv0.0: K3's 4-channel layer)
+
+        def arrange(iota):
+            if transposed_flipped:
+                return _transposed_flipped(iota)
+            return iota if cin != 3 else torch.cat((iota, torch.zeros_like(iota[:, :1])), 1)   # (the fourth channel selects the zero)
+        return _derive_index("pack_index_mfma_fpn", (cout, cin, ksize, ksize), arrange,
+                             lambda w: pack_mfma(w, lin, lout, CONV_S1 if ksize == 3 else CONV2D_K1, 1), False)
     return _pack_index(("fpn", int(cin), int(cout), int(ksize), bool(transposed_flipped)), build, device)
 
 
@@ -1294,11 +1289,8 @@ def _wgrad_fpn_dims(x: torch.Tensor, gy: torch.Tensor, ksize: int):
 
 def conv2d_wgrad_fpn_workspace(Cin: int, Cout: int, ksize: int, D: int, H: int, W: int, device) -> torch.Tensor:
     """K3f's workspace, one per (shape class, device, stream): its size does not depend on D, H, W."""
-    n = _lib.load().dmvs_conv2d_wgrad_fpn_workspace(Cin, Cout, ksize, D, H, W)
-    if n <= 0:
-        raise _lib.DmvsError(f"conv2d_wgrad_fpn: (Cin, Cout, kernel) = {(Cin, Cout, ksize)}, planes {(D, H, W)} is not covered by the "
-                             "weight-gradient kernel")
-    return _workspace("k3f", n, device)
+    dims = (Cin, Cout, ksize, D, H, W)
+    return _wgrad_workspace("conv2d_wgrad_fpn", "k3f", _lib.load().dmvs_conv2d_wgrad_fpn_workspace(*dims), dims, device)
 
 
 def conv2d_wgrad_fpn(x: torch.Tensor, gy: torch.Tensor, ksize: int, out: Optional[torch.Tensor] = None,
@@ -1312,25 +1304,20 @@ def conv2d_wgrad_fpn(x: torch.Tensor, gy: torch.Tensor, ksize: int, out: Optiona
     _req(x, gy, out, bias_out, workspace)
     Cin, Cout, D, H, W = _wgrad_fpn_dims(x, gy, ksize)
     if accumulate and out is None:
-        raise _lib.DmvsError("conv2d_wgrad_fpn: accumulate needs the buffer to add to (out)")
+        raise _no_buffer("conv2d_wgrad_fpn")
     if bias_out is not None:
         if (Cin, Cout, ksize) not in FPN_BIAS_SHAPES:
             raise _lib.DmvsError(f"conv2d_wgrad_fpn: the layer {(Cin, Cout, ksize)} has no bias (only {FPN_BIAS_SHAPES} have)")
         if bias_out.numel() != Cout:
             raise _lib.DmvsError(f"conv2d_wgrad_fpn: bias_out {tuple(bias_out.shape)} is not a [{Cout}] bias")
-    if out is None:
-        out = torch.empty((Cout, Cin, ksize, ksize), dtype=torch.float32, device=x.device)
-    elif out.numel() != Cout * Cin * ksize * ksize:
-        raise _lib.DmvsError(f"conv2d_wgrad_fpn: out {tuple(out.shape)} is not a [{Cout},{Cin},{ksize},{ksize}] weight")
-    if workspace is None:
-        workspace = conv2d_wgrad_fpn_workspace(Cin, Cout, ksize, D, H, W, x.device)
-    elif workspace.numel() < _lib.load().dmvs_conv2d_wgrad_fpn_workspace(Cin, Cout, ksize, D, H, W):
-        raise _lib.DmvsError("conv2d_wgrad_fpn: workspace too small")
+    lib, dims = _lib.load(), (Cin, Cout, ksize, D, H, W)
+    out = _wgrad_out("conv2d_wgrad_fpn", out, accumulate, (Cout, Cin, ksize, ksize), x)
+    workspace = _wgrad_workspace("conv2d_wgrad_fpn", "k3f", lib.dmvs_conv2d_wgrad_fpn_workspace(*dims), dims, x.device, workspace)
     cost = None
     if timer is not None:
         nt = ksize * ksize * Cin * Cout
         cost = (2.0 * nt * D * H * W, 4.0 * ((Cin + Cout) * D * H * W + nt), None)
-    _launch(_lib.load().dmvs_conv2d_wgrad_fpn,
+    _launch(lib.dmvs_conv2d_wgrad_fpn,
             (_ptr(x), _ptr(gy), _ptr(out), _ptr(bias_out), _ptr(workspace), Cin, Cout, D, H, W, ksize, 1 if accumulate else 0),
             f"wgrad_fpn_{Cin}to{Cout}k{ksize}", "wgrad_fpn", x, (gy, out, bias_out, workspace), False, "conv2d_wgrad_fpn", cost)
     _log("conv2d_wgrad_fpn")   # two dispatches per call: the partials and their sum

@@ -441,6 +441,31 @@ def test_bias_alone_launches_the_weight_gradient_kernel(fake):
     assert tuple(gb.shape) == (32,) and lib.calls[-1] == ("dmvs_conv2d_wgrad_fpn", (8, 32, 1, H, W, 1, 0))
 
 
+def test_a_moved_bias_leaves_one_forward_layer_behind(fake):
+    """The forward layer of a lateral is cached under a slot that carries the bias's data pointer and device: a bias that moved to a new
+    tensor between two forwards evicts the old entry, so exactly one bias-keyed entry stays in the module's cache; the launches of a
+    forward + backward on a batch of 2 are those test_layer_forward_backward_launches lists."""
+    m = _ctor(16, 32, 1, True)
+    lib = fake()
+    fwd, dgrad, wgrad = _launches(16, 32, 1)
+    x = torch.zeros(2, 16, H, W, requires_grad=True)
+    m(x)
+    (slot,) = [s for s in m._packed if isinstance(s, tuple)]
+    assert slot == (False, m.bias.data_ptr(), m.bias.device) and m._packed[slot][1].shift.data_ptr() == m.bias.data_ptr()
+    m(x)
+    assert [s for s in m._packed if isinstance(s, tuple)] == [slot]   # the same bias: the same entry
+    old = m.bias.data    # (kept alive: the new tensor cannot take its address)
+    m.bias.data = old.clone()
+    del lib.calls[:]
+    y = m(x)
+    (moved,) = [s for s in m._packed if isinstance(s, tuple)]
+    assert moved == (False, m.bias.data_ptr(), m.bias.device) and moved != slot
+    assert m._packed[moved][1].shift.data_ptr() == m.bias.data_ptr() != old.data_ptr()
+    torch.autograd.grad(y, [x, m.weight, m.bias], torch.zeros_like(y))
+    assert lib.calls == [fwd] * 2 + [dgrad] * 2 + [wgrad(0), wgrad(1)]
+    assert sorted(map(str, m._packed)) == sorted(map(str, [moved, True]))   # ... beside the data gradient's layer
+
+
 def test_conv_fn_keeps_its_signature(fake):
     lib = fake()
     x, w = torch.zeros((1, 16, 1, H, W), requires_grad=True), torch.zeros((16, 16, 3, 3), requires_grad=True)

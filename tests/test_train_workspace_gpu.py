@@ -1,4 +1,4 @@
-"""GPU (-m gpu, no kernel launch): the cached workspaces of K3g, K3h, K2g and K5 are one buffer per device however the device is
+"""GPU (-m gpu, no kernel launch): the cached workspaces of K3g, K3h, K2g, K3k, K3f and K5 are one buffer per device however the device is
 spelled -- "cuda", the current device with its index, a tensor's ``.device`` -- at the smallest shape each kernel covers, and another
 buffer for another size (K2g's size is the same for both of its shapes and every volume) or another kernel."""
 import pytest
@@ -13,6 +13,8 @@ GETTERS = [
     (ops.conv3d_wgrad_workspace, (16, 1, 1, 1, 3), (32, 1, 1, 1, 3)),      # C, D, H, W, kdepth
     (ops.conv3d_wgrad_s2_workspace, (16, 1, 1, 1, 3), (32, 1, 1, 1, 3)),   # Ca, Dc, Hc, Wc, kdepth
     (ops.conv3d_wgrad_c2_workspace, (2, 8, 1, 1, 1), None),                # Cin, Cout, D, H, W
+    (ops.conv2d_k5s2_wgrad_workspace, (16, 1, 1, 1), (32, 1, 1, 1)),       # Ca, D, Hf, Wf
+    (ops.conv2d_wgrad_fpn_workspace, (3, 8, 3, 1, 1, 1), (8, 8, 3, 1, 1, 1)),   # Cin, Cout, kernel, D, H, W
     (ops.bn_workspace, (8, 1, 2), (16, 1, 2)),                             # C, B, V
 ]
 
