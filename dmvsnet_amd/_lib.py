@@ -46,6 +46,9 @@ SIGNATURES = {
     "dmvs_warp_corr_backward_det_workspace": (ctypes.c_long, [_i, _i, _i, _i]),
     "dmvs_warp_corr_backward_det": (_i, [_p, ctypes.POINTER(_p), _i, _p, _p, _p, _p, ctypes.POINTER(_p), _i, _i, _i, _i, _p,
                                          ctypes.c_size_t, _i, _p]),
+    "dmvs_warp_corr_backward_presum_cap": (ctypes.c_long, [_i, _i, _i]),
+    "dmvs_warp_corr_backward_presum": (_i, [_p, ctypes.POINTER(_p), _i, _p, _p, _p, _p, ctypes.POINTER(_p), _i, _i, _i, _i, _i, _p,
+                                            ctypes.c_size_t, _i, _p, _p]),
     "dmvs_nchw_to_q4": (_i, [_p, ctypes.c_long, _i, _i, _i, _i, _p, _p]),
     "dmvs_conv3d_direct": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "dmvs_conv3d_mfma": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),

@@ -19,7 +19,9 @@ bitwise reproducible.  The source-view gradients are accumulated with floating-p
 fp32 rounding.  In DETERMINISTIC mode (``deterministic=True``, or ``None`` under ``torch.use_deterministic_algorithms(True)``)
 they are accumulated in fixed point instead (``ops.warp_corr_backward_det``: the same scatter kernel on csrc/warp_corr_bwd_det.h's
 ``FixedSink``): bitwise reproducible, a pure function of the sample's inputs -- independent of the batch around it and of which
-other views want a gradient.
+other views want a gradient.  ``presum=True`` takes the source scatter of either mode through ``ops.warp_corr_backward_presum``
+(csrc/warp_corr_bwd_presum.h: a workgroup's addends are summed in an LDS window before they reach memory): the same bits in
+deterministic mode, the same addends in another order of the fp32 sum otherwise.  Off by default.
 """
 from __future__ import annotations
 
@@ -37,12 +39,14 @@ SUPPORTED_C = (8, 16, 32)
 launch_counts = {"bwd_ref": 0, "bwd_src_views": 0}
 # the same for backwards taken in deterministic mode (which leave ``launch_counts`` alone)
 det_launch_counts = {"bwd_ref": 0, "bwd_src_views": 0}
+# the same for backwards taken with ``presum=True``, in either mode (which leave both dicts above alone)
+presum_launch_counts = {"bwd_ref": 0, "bwd_src_views": 0}
 
 
 class _CostAggFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, deterministic, proj_matrices, depth_values, *features):
-        ctx.deterministic = bool(deterministic)
+    def forward(ctx, mode, proj_matrices, depth_values, *features):
+        ctx.deterministic, ctx.presum = (bool(m) for m in mode)
         B, C, H, W = features[0].shape
         D = depth_values.shape[1]
         V = len(features)
@@ -76,29 +80,34 @@ class _CostAggFn(torch.autograd.Function):
                 grads[v] = (torch.empty if det else torch.zeros)((B, C, H, W), dtype=torch.float32, device=q4.device)
         if any(need):
             nact = sum(int(n) for n in need[1:])
-            counts = det_launch_counts if det else launch_counts
+            counts = presum_launch_counts if ctx.presum else det_launch_counts if det else launch_counts
             run, mode = ops.warp_corr_backward, {}
-            if det:
+            if ctx.presum:
+                run, mode = ops.warp_corr_backward_presum, {"deterministic": det}
+            elif det:
                 run = ops.warp_corr_backward_det
+            if det:
                 if nact:   # one workspace for the batch: the samples run one after the other on one stream
                     nbytes = ops.warp_corr_backward_det_workspace(C, H, W, nact)
-                    mode = {"workspace": torch.empty((nbytes // 8,), dtype=torch.int64, device=q4.device)}
+                    mode["workspace"] = torch.empty((nbytes // 8,), dtype=torch.int64, device=q4.device)
             for b in range(B):
                 run(q4[b, 0], [q4[b, v] for v in range(1, V)], proj12[b], depth[b], gsim[b],
                     None if grads[0] is None else grads[0][b], [None if grads[v] is None else grads[v][b] for v in range(1, V)], **mode)
                 counts["bwd_ref"] += int(need[0])
                 counts["bwd_src_views"] += nact
-        # the mode; cameras, hypotheses: the reference's grid is built under no_grad (module.py:222-243) -- no gradient exists
+        # the mode (deterministic, presum); cameras, hypotheses: the reference's grid is built under no_grad (module.py:222-243) -- no gradient exists
         return (None, None, None, *grads)
 
 
 def cost_agg(features: Sequence[torch.Tensor], proj_matrices: torch.Tensor, depth_values: torch.Tensor,
-             deterministic: Optional[bool] = None) -> torch.Tensor:
+             deterministic: Optional[bool] = None, presum: bool = False) -> torch.Tensor:
     """features: V tensors [B,C,H,W] fp32 on a HIP device, reference view first; proj_matrices [B,V,2,4,4]; depth_values
     [B,D,H,W] -> similarity volume [B,2,D,H,W] (group k = mean over g of warped[2g+k] * ref[2g+k], summed over the source
     views), differentiable with respect to the feature maps.  ``deterministic``: True / False force the mode of the backward's
     source-view gradients (fixed-point, bitwise reproducible / fp32 atomics); None follows
-    ``torch.are_deterministic_algorithms_enabled()`` at the time of this forward.  The forward and dRef are the same either way."""
+    ``torch.are_deterministic_algorithms_enabled()`` at the time of this forward.  ``presum``: True takes the backward's source scatter, in
+    whichever mode ``deterministic`` resolves to, through ``ops.warp_corr_backward_presum``.  The forward and dRef are the same either
+    way."""
     features = list(features)
     V = len(features)
     for t in (*features, proj_matrices, depth_values):
@@ -121,14 +130,14 @@ def cost_agg(features: Sequence[torch.Tensor], proj_matrices: torch.Tensor, dept
         raise _lib.DmvsError(f"cost_agg: depth_values must be [B,D,H,W] with the features' B, H, W, got {tuple(depth_values.shape)}")
     if deterministic is None:
         deterministic = torch.are_deterministic_algorithms_enabled()
-    return _CostAggFn.apply(bool(deterministic), proj_matrices, depth_values, *features)
+    return _CostAggFn.apply((bool(deterministic), bool(presum)), proj_matrices, depth_values, *features)
 
 
 class DiffCostAgg(nn.Module):
     """Drop-in for the reference's ``CostAgg`` (networks/mvsnet.py:102-153, "variance" mode) that autograd can differentiate.
     Owns no parameters; train and eval mode compute the same thing."""
 
-    def __init__(self, mode="variance", in_channels=None, deterministic=None):
+    def __init__(self, mode="variance", in_channels=None, deterministic=None, presum=False):
         super().__init__()
         assert mode in ("variance", "adaptive"), "Don't support {}!".format(mode)
         if mode == "adaptive":
@@ -136,6 +145,7 @@ class DiffCostAgg(nn.Module):
                                       "(SURVEY.md section 2 row 8) and is not built")
         self.mode = mode
         self.deterministic = deterministic   # as cost_agg's keyword
+        self.presum = bool(presum)           # as cost_agg's keyword
 
     def forward(self, features, proj_matrices, depth_values, stage_idx=None):
-        return cost_agg(features, proj_matrices, depth_values, deterministic=self.deterministic)
+        return cost_agg(features, proj_matrices, depth_values, deterministic=self.deterministic, presum=self.presum)

@@ -698,5 +698,6 @@ extern "C" int dmvs_warp_corr_q4_f16(const void* ref_q4h, const void* const* src
 
 // ------------------------------------------------------------------------------------------------
 // K1b: the backward kernels (dRef gather, dSrc scatter), dmvs_warp_corr_backward and, through warp_corr_bwd_det.h, the
-// deterministic mode dmvs_warp_corr_backward_det
+// deterministic mode dmvs_warp_corr_backward_det and, through warp_corr_bwd_presum.h, the pre-summed scatter
+// dmvs_warp_corr_backward_presum
 #include "warp_corr_bwd.h"

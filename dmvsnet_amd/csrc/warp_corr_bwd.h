@@ -139,14 +139,21 @@ struct AtomicSink {
     __device__ __forceinline__ static bool idle(Scale) { return false; }
     __device__ __forceinline__ float* dest(const WarpBwdArgs& a, int i, size_t) const { return a.gsrc[i]; }
     __device__ __forceinline__ static void add(float* p, float t, Scale) { atomicAdd(p, t); }
+    // the pre-summed scatter (warp_corr_bwd_presum.h): what a window element holds, what an addend joins it as, one sum's global add
+    using Acc = float;
+    __device__ __forceinline__ static Acc quant(float t, Scale) { return t; }
+    __device__ __forceinline__ static void flush(float* p, Acc s, Scale) { atomicAdd(p, s); }
 };
 
 // the deterministic mode's scale, pre-pass, sink and finalize; needs WarpBwdArgs, needed by the launcher
 #include "warp_corr_bwd_det.h"
+// the pre-summed form of the scatter; needs both sinks, needed by the launcher
+#include "warp_corr_bwd_presum.h"
 
-// ws: null for the default mode, else the deterministic mode's workspace (variant: its decomposition, 0 or 1)
+// ws: null for the default mode, else the deterministic mode's workspace (variant bit 0: its decomposition).  ps: null for the plain
+// scatter, else the pre-summed one in the same mode (variant bit 1: its test capacity).
 template <int NQ>
-static int launch_warp_bwd(const WarpBwdArgs& a, long long* ws, int variant, hipStream_t st) {
+static int launch_warp_bwd(const WarpBwdArgs& a, long long* ws, int variant, const WarpBwdPresum* ps, hipStream_t st) {
     constexpr int QPT = 2, C = NQ * 4;
     const dim3 block(kBwdTX, kBwdTY);
     const int gx = ceil_div(a.W, kBwdTX), gy = ceil_div(a.H, kBwdTY), nqg = NQ / QPT;
@@ -156,11 +163,12 @@ static int launch_warp_bwd(const WarpBwdArgs& a, long long* ws, int variant, hip
         if (e != hipSuccess) return (int)e;
     }
     if (a.nact > 0) {
-        const int nch = ceil_div(a.D, variant ? 4 : 8);
+        const int nch = ceil_div(a.D, (variant & 1) ? 4 : 8);
         if ((long)a.nact * nqg * nch > 65535) return DMVS_EUNSUPPORTED;
         const dim3 grid(gx, gy, a.nact * nqg * nch);
         if (!ws) {
-            warp_corr_bwd_src_kernel<NQ, QPT, 8, false><<<grid, block, 0, st>>>(a, nqg, nch, AtomicSink{});
+            if (ps) launch_presum_scatter<NQ, QPT>(a, grid, block, nqg, nch, AtomicSink{}, variant, *ps, st);
+            else warp_corr_bwd_src_kernel<NQ, QPT, 8, false><<<grid, block, 0, st>>>(a, nqg, nch, AtomicSink{});
         } else {
             const size_t plane = (size_t)a.H * a.W, per_view = (size_t)C * plane, ng = 2 * (size_t)a.D * plane;
             const int kcap = std::min(62 - det_ceil_log2((unsigned long long)a.D * plane), 50);
@@ -172,7 +180,8 @@ static int launch_warp_bwd(const WarpBwdArgs& a, long long* ws, int variant, hip
             const unsigned nb = (unsigned)std::min((size_t)256, (std::max(ng, per_view) + 2047) / 2048);
             warp_corr_det_absmax_kernel<<<dim3(nb, 2), 256, 0, st>>>(a.gsim, ng, a.ref, per_view, reinterpret_cast<unsigned*>(mx));
             const FixedSink sink{ws, mx, kcap, lc};
-            if (variant) warp_corr_bwd_src_kernel<NQ, QPT, 4, true><<<grid, block, 0, st>>>(a, nqg, nch, sink);
+            if (ps) launch_presum_scatter<NQ, QPT>(a, grid, block, nqg, nch, sink, variant, *ps, st);
+            else if (variant) warp_corr_bwd_src_kernel<NQ, QPT, 4, true><<<grid, block, 0, st>>>(a, nqg, nch, sink);
             else warp_corr_bwd_src_kernel<NQ, QPT, 8, false><<<grid, block, 0, st>>>(a, nqg, nch, sink);
             const unsigned fb = (unsigned)((per_view + 255) / 256);   // < 2^21: per_view < 2^29
             warp_corr_det_finalize_kernel<<<dim3(fb, a.nact), 256, 0, st>>>(a, ws, per_view, 2, per_view, mx, kcap, lc);
@@ -182,14 +191,16 @@ static int launch_warp_bwd(const WarpBwdArgs& a, long long* ws, int variant, hip
     DMVS_LAUNCH_CHECK();
 }
 
-// Both public entries.  det: the deterministic mode, which needs an 8-byte aligned workspace of
-// dmvs_warp_corr_backward_det_workspace() bytes once a source gradient is wanted, and a variant of 0 or 1.
-static int warp_corr_bwd_entry(bool det, const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
-                               const float* depth_dhw, const float* gsim_2dhw, float* gref_chw, float* const* gsrc_chw, int C,
-                               int D, int H, int W, void* workspace, size_t workspace_bytes, int variant, dmvs_stream_t stream) {
+// The public entries.  det: the deterministic mode, which needs an 8-byte aligned workspace of
+// dmvs_warp_corr_backward_det_workspace() bytes once a source gradient is wanted, and a variant of 0 or 1.  ps: the pre-summed
+// scatter in either mode (variant 0..3), null for the plain one.
+static int warp_corr_bwd_entry(bool det, const WarpBwdPresum* ps, const float* ref_q4, const float* const* src_q4, int nsrc,
+                               const float* proj12, const float* depth_dhw, const float* gsim_2dhw, float* gref_chw,
+                               float* const* gsrc_chw, int C, int D, int H, int W, void* workspace, size_t workspace_bytes, int variant,
+                               dmvs_stream_t stream) {
     if (!ref_q4 || !src_q4 || !proj12 || !depth_dhw || !gsim_2dhw) return DMVS_EINVAL;
     if (nsrc < 1 || nsrc > DMVS_MAX_SRC_VIEWS || D < 1 || H < 1 || W < 1) return DMVS_EINVAL;
-    if (det && variant != 0 && variant != 1) return DMVS_EINVAL;
+    if (ps ? (variant < 0 || variant > 3) : (det && variant != 0 && variant != 1)) return DMVS_EINVAL;
     if (C != 8 && C != 16 && C != 32) return DMVS_EUNSUPPORTED;
     if ((long)H * W * C >= (1L << 29)) return DMVS_EUNSUPPORTED;   // 32-bit tap offsets
     WarpBwdArgs a;
@@ -207,23 +218,34 @@ static int warp_corr_bwd_entry(bool det, const float* ref_q4, const float* const
     hipStream_t st = (hipStream_t)stream;
     long long* ws = det && a.nact > 0 ? static_cast<long long*>(workspace) : nullptr;
     switch (C) {
-        case 8: return launch_warp_bwd<2>(a, ws, variant, st);
-        case 16: return launch_warp_bwd<4>(a, ws, variant, st);
-        default: return launch_warp_bwd<8>(a, ws, variant, st);
+        case 8: return launch_warp_bwd<2>(a, ws, variant, ps, st);
+        case 16: return launch_warp_bwd<4>(a, ws, variant, ps, st);
+        default: return launch_warp_bwd<8>(a, ws, variant, ps, st);
     }
 }
 
 extern "C" int dmvs_warp_corr_backward(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
                                        const float* depth_dhw, const float* gsim_2dhw, float* gref_chw,
                                        float* const* gsrc_chw, int C, int D, int H, int W, dmvs_stream_t stream) {
-    return warp_corr_bwd_entry(false, ref_q4, src_q4, nsrc, proj12, depth_dhw, gsim_2dhw, gref_chw, gsrc_chw, C, D, H, W, nullptr,
-                               0, 0, stream);
+    return warp_corr_bwd_entry(false, nullptr, ref_q4, src_q4, nsrc, proj12, depth_dhw, gsim_2dhw, gref_chw, gsrc_chw, C, D, H, W,
+                               nullptr, 0, 0, stream);
 }
 
 extern "C" int dmvs_warp_corr_backward_det(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
                                            const float* depth_dhw, const float* gsim_2dhw, float* gref_chw,
                                            float* const* gsrc_chw, int C, int D, int H, int W, void* workspace,
                                            size_t workspace_bytes, int variant, dmvs_stream_t stream) {
-    return warp_corr_bwd_entry(true, ref_q4, src_q4, nsrc, proj12, depth_dhw, gsim_2dhw, gref_chw, gsrc_chw, C, D, H, W, workspace,
-                               workspace_bytes, variant, stream);
+    return warp_corr_bwd_entry(true, nullptr, ref_q4, src_q4, nsrc, proj12, depth_dhw, gsim_2dhw, gref_chw, gsrc_chw, C, D, H, W,
+                               workspace, workspace_bytes, variant, stream);
+}
+
+// K1b with the pre-summed scatter (warp_corr_bwd_presum.h) in place of the plain one: the same part of the reference as the two
+// entries above -- the backward autograd records for CostAgg.forward (mvsnet.py:111-153) over homo_warping (module.py:212-251).
+extern "C" int dmvs_warp_corr_backward_presum(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
+                                              const float* depth_dhw, const float* gsim_2dhw, float* gref_chw,
+                                              float* const* gsrc_chw, int C, int D, int H, int W, int det, void* workspace,
+                                              size_t workspace_bytes, int variant, unsigned* path_counts, dmvs_stream_t stream) {
+    const WarpBwdPresum ps{path_counts};
+    return warp_corr_bwd_entry(det != 0, &ps, ref_q4, src_q4, nsrc, proj12, depth_dhw, gsim_2dhw, gref_chw, gsrc_chw, C, D, H, W,
+                               workspace, workspace_bytes, variant, stream);
 }

@@ -82,9 +82,13 @@ struct FixedSink {
     __device__ __forceinline__ unsigned long long* dest(const WarpBwdArgs&, int i, size_t per_view) const {
         return reinterpret_cast<unsigned long long*>(ws) + (size_t)i * per_view;
     }
-    __device__ __forceinline__ static void add(unsigned long long* p, float t, const Scale& sc) {
-        atomicAdd(p, (unsigned long long)__double2ll_rn(ldexp((double)t, sc.k)));
+    // the pre-summed scatter (warp_corr_bwd_presum.h) sums the SAME q in LDS first and adds each sum once
+    using Acc = unsigned long long;
+    __device__ __forceinline__ static Acc quant(float t, const Scale& sc) {
+        return (unsigned long long)__double2ll_rn(ldexp((double)t, sc.k));
     }
+    __device__ __forceinline__ static void add(unsigned long long* p, float t, const Scale& sc) { atomicAdd(p, quant(t, sc)); }
+    __device__ __forceinline__ static void flush(unsigned long long* p, Acc s, const Scale&) { atomicAdd(p, s); }
 };
 
 // gsrc[view0 + blockIdx.y][e] = (float)((double)sum * 2^-k) for e in [lo, hi), lo = lo0 on the first wanted view and 0 on the

@@ -329,8 +329,10 @@ def nchw_to_q4(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     return dst
 
 
-def _warp_corr_backward(what: str, ref_q4, src_q4, proj12, depth_dhw, gsim, gref, gsrc, workspace, variant: int, det: bool) -> None:
-    """Both modes of K1b: validation (errors name the public function ``what``), the two pointer arrays and the call."""
+def _warp_corr_backward(what: str, ref_q4, src_q4, proj12, depth_dhw, gsim, gref, gsrc, workspace, variant: int, det: bool,
+                        presum: Optional[tuple] = None) -> None:
+    """Both modes of K1b: validation (errors name the public function ``what``), the two pointer arrays and the call.  ``presum``:
+    None, or ``(path_counts,)`` for the pre-summed scatter's entry, which takes the mode as an argument."""
     src_q4, gsrc = list(src_q4), list(gsrc)
     live = [g for g in gsrc if g is not None]
     if depth_dhw.dim() != 3 or ref_q4.dim() != 4 or ref_q4.shape[-1] != 4:
@@ -347,11 +349,25 @@ def _warp_corr_backward(what: str, ref_q4, src_q4, proj12, depth_dhw, gsim, gref
     for g in (gref, *live):
         if g is not None and tuple(g.shape) != (C, H, W):
             raise _lib.DmvsError(f"{what}: gradient {tuple(g.shape)}, expected {(C, H, W)}")
+    counts = None
+    if presum is not None:   # what needs no device is refused before a device is asked for
+        counts, = presum
+        if int(variant) not in (0, 1, 2, 3):
+            raise _lib.DmvsError(f"{what}: variant must be 0..3 (bit 0: decomposition, bit 1: test capacity), got {variant}")
+        if det and live and workspace is not None and workspace.numel() * 8 < warp_corr_backward_det_workspace(C, H, W, len(live)):
+            raise _lib.DmvsError(f"{what}: a workspace of {workspace.numel() * 8} bytes, {len(live)} wanted views need "
+                                 f"{warp_corr_backward_det_workspace(C, H, W, len(live))}")
+        if counts is not None and not (counts.dtype == torch.int32 and counts.numel() == 3 and counts.is_contiguous()):
+            raise _lib.DmvsError(f"{what}: path_counts must be three contiguous int32 words (windowed, direct, empty)")
     _req(ref_q4, proj12, depth_dhw, gsim, gref, *src_q4, *live)
+    if counts is not None and not counts.is_cuda:
+        raise _lib.DmvsError(f"{what}: path_counts must be on the HIP device")
     if gref is None and not live:
         return
     args = [_ptr(ref_q4), (ctypes.c_void_p * nsrc)(*[s.data_ptr() for s in src_q4]), nsrc, _ptr(proj12), _ptr(depth_dhw), _ptr(gsim),
             _ptr(gref), (ctypes.c_void_p * nsrc)(*[None if g is None else g.data_ptr() for g in gsrc]), C, D, H, W]
+    if presum is not None:
+        args.append(int(det))
     if det:
         if live and workspace is None:
             need = warp_corr_backward_det_workspace(C, H, W, len(live))
@@ -362,6 +378,10 @@ def _warp_corr_backward(what: str, ref_q4, src_q4, proj12, depth_dhw, gsim, gref
                 raise _lib.DmvsError(f"{what}: the workspace must be a contiguous int64 HIP tensor")
             nbytes = workspace.numel() * 8
         args += [_ptr(workspace), nbytes, int(variant)]
+    elif presum is not None:
+        args += [None, 0, int(variant)]
+    if presum is not None:
+        args.append(_ptr(counts))
     _lib.check(getattr(_lib.load(), "dmvs_" + what)(*args, _stream()), "dmvs_" + what)
 
 
@@ -386,6 +406,25 @@ def warp_corr_backward_det(ref_q4: torch.Tensor, src_q4: Sequence[torch.Tensor],
     kernels clear it).  ``variant``: launch-configuration knob (0 default, 1 another decomposition, the same bits).  Not logged as
     a launch family."""
     _warp_corr_backward("warp_corr_backward_det", ref_q4, src_q4, proj12, depth_dhw, gsim, gref, gsrc, workspace, variant, True)
+
+
+def warp_corr_backward_presum_cap(C: int, deterministic: bool, variant: int = 0) -> int:
+    """Texels an LDS window of ``warp_corr_backward_presum`` holds: a workgroup whose taps span more falls back to global adds."""
+    return int(_lib.load().dmvs_warp_corr_backward_presum_cap(C, int(bool(deterministic)), int(variant)))
+
+
+def warp_corr_backward_presum(ref_q4: torch.Tensor, src_q4: Sequence[torch.Tensor], proj12: torch.Tensor, depth_dhw: torch.Tensor,
+                              gsim: torch.Tensor, gref: Optional[torch.Tensor], gsrc: Sequence[Optional[torch.Tensor]],
+                              deterministic: bool = False, workspace: Optional[torch.Tensor] = None, variant: int = 0,
+                              path_counts: Optional[torch.Tensor] = None) -> None:
+    """K1b with the pre-summed source scatter: a workgroup sums its addends in an LDS window over the bounding box of its taps and
+    issues one global add per window element (a box above ``warp_corr_backward_presum_cap`` texels falls back to the plain
+    scatter's adds).  ``deterministic=False``: as ``warp_corr_backward`` (ADDS into zeroed gsrc; the same addends, another order of
+    the fp32 sum); True: as ``warp_corr_backward_det`` (``workspace``; every wanted gsrc WRITTEN; the same bits).  ``variant``: bit 0
+    the other decomposition, bit 1 a test capacity of 256 texels.  ``path_counts``: three zeroed int32 words on the device, to which
+    the workgroups add how many took the window, fell back, had no tap inside.  Not logged as a launch family."""
+    _warp_corr_backward("warp_corr_backward_presum", ref_q4, src_q4, proj12, depth_dhw, gsim, gref, gsrc,
+                        workspace if deterministic else None, variant, bool(deterministic), presum=(path_counts,))
 
 
 def warp_corr(ref: torch.Tensor, src: Sequence[torch.Tensor], proj12: torch.Tensor, depth_dhw: torch.Tensor,

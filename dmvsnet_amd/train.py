@@ -154,11 +154,13 @@ def _check_inputs(what, imgs, proj_matrices, depth_values):
 class DiffMVSNet(nn.Module):
     """The reference's ``MVSNet`` on the differentiable gfx950 parts; see the module's text.  Beyond the reference's arguments:
     ``deterministic`` goes to ``DiffCostAgg`` (True: bitwise reproducible source-view gradients; None follows
-    ``torch.are_deterministic_algorithms_enabled()``); ``prob_volume=True`` adds the softmax volume to the outputs (the regression loss
-    never reads it); ``verbose=True`` prints the configuration as the reference does on construction."""
+    ``torch.are_deterministic_algorithms_enabled()``); ``presum`` goes there too (True: the backward's source scatter pre-summed in
+    LDS windows, in whichever mode ``deterministic`` resolves to; the default False is the plain scatter);
+    ``prob_volume=True`` adds the softmax volume to the outputs (the regression loss never reads it); ``verbose=True`` prints the configuration as the reference does on construction."""
 
     def __init__(self, ndepths, depth_interval_ratio, cr_base_chs=None, fea_mode="fpn", agg_mode="variance", depth_mode="regression",
-                 winner_take_all_to_generate_depth=True, inverse_depth=False, deterministic=None, prob_volume=False, verbose=False):
+                 winner_take_all_to_generate_depth=True, inverse_depth=False, deterministic=None, prob_volume=False, verbose=False,
+                 presum=False):
         super().__init__()
         if cr_base_chs is None:
             cr_base_chs = [8] * len(ndepths)
@@ -177,7 +179,7 @@ class DiffMVSNet(nn.Module):
             print("agg_mode:", agg_mode)
             print("depth_mode:", depth_mode)
         self.feature = DiffFeatureNet(base_channels=8, stride=4, num_stage=self.num_stage, mode=fea_mode)
-        self.cost_aggregation = DiffCostAgg(agg_mode, self.feature.out_channels, deterministic=deterministic)
+        self.cost_aggregation = DiffCostAgg(agg_mode, self.feature.out_channels, deterministic=deterministic, presum=presum)
         self.cost_regularization = nn.ModuleList([DiffCostRegNet(2, self.cr_base_chs[i], stage=i) for i in range(self.num_stage)])
         self.cost_regularization_refine = nn.ModuleList([DiffCostRegNetRefine(2, self.cr_base_chs[i], stage=i)
                                                          for i in range(self.num_stage)])

@@ -232,6 +232,27 @@ int dmvs_warp_corr_backward_det(const float* ref_q4, const float* const* src_q4,
                                 int C, int D, int H, int W, void* workspace, size_t workspace_bytes, int variant,
                                 dmvs_stream_t stream);
 
+/* K1b with a PRE-SUMMED source scatter (additive, same version; csrc/warp_corr_bwd_presum.h; docs/kernels/K1b_warp_corr_backward.md,
+ * "Pre-summed scatter"): the backward autograd records for CostAgg.forward (mvsnet.py:111-153) over homo_warping
+ * (module.py:212-251), as the two entries above, in either of their modes.  A workgroup (64 x 4 pixels, one plane chunk) takes
+ * the bounding box of its in-image taps, sums its addends in an LDS window of that box and issues one global add per window
+ * element that is not zero; a box above the capacity falls back to the plain scatter's global adds per tap, an empty box adds
+ * nothing.  The addends are those of the entries above, formed by the same code.
+ *   det          0: fp32 atomics into the caller's ZEROED gsrc_chw (workspace ignored), equal to dmvs_warp_corr_backward to fp32
+ *                rounding (another order of the same sum); 1: the workspace, pre-pass, clear and finalize of
+ *                dmvs_warp_corr_backward_det, and its bits (integer sums do not depend on grouping)
+ *   variant      0..3, else DMVS_EINVAL.  Bit 0 as dmvs_warp_corr_backward_det's 1 (4-plane chunks, planes and workgroups in
+ *                reverse); bit 1: a test capacity of 256 texels.  The same values (det = 1: bits) for every variant.
+ *   path_counts  NULL, or three device words the caller has zeroed: workgroups that took the window, the fallback, had no tap
+ *   gref_chw     as above: the same kernel, the same bits
+ * dmvs_warp_corr_backward_presum_cap: the window capacity in texels of (C, det, variant); 0 for arguments the entry refuses.
+ * Limits and refusals otherwise as the entries above. */
+long dmvs_warp_corr_backward_presum_cap(int C, int det, int variant);
+int dmvs_warp_corr_backward_presum(const float* ref_q4, const float* const* src_q4, int nsrc, const float* proj12,
+                                   const float* depth_dhw, const float* gsim_2dhw, float* gref_chw, float* const* gsrc_chw,
+                                   int C, int D, int H, int W, int det, void* workspace, size_t workspace_bytes, int variant,
+                                   unsigned* path_counts, dmvs_stream_t stream);
+
 /* [C_total][H][W] planar slice c0..c0+C with a channel stride of chan_stride floats -> quad-planar [C/4][H][W][4]:
  * layout glue between torch feature maps (module.py:326-336: the stageK / stageK_c `split` halves are views that keep
  * the parent's channel stride; a batch sample is a pointer offset) and dmvs_warp_corr_q4 / dmvs_warp_corr_backward.

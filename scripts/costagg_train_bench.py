@@ -20,6 +20,12 @@ reference gradient switched off: clear + pre-pass + scatter + finalize), its wor
 atomics (4 taps * C * 8 B per sample) over the scatter kernel's time, and the four steps apart -- from the device times of
 torch.profiler where it records them (det_parts_ms: clear, prepass, scatter, finalize), and always by difference
 (det_bwd_src_zero_gsim_ms: the same launch on gsim = 0, where the scatter exits at once, and det_clear_ms: a memset of the workspace).
+
+--presum (implies --deterministic) adds a fourth and a fifth arm, cost_agg(..., presum=True) in the atomic and in the deterministic mode
+(csrc/warp_corr_bwd_presum.h: the scatter pre-summed in LDS windows), to the same alternating windows, and per pass the four source-
+gradient launches alone in alternating windows of their own (presum_src_ms: atomic, presum, det, presum_det; the reference gradient
+switched off), with the share of workgroups that took the window, fell back to global adds per tap or had no tap inside
+(presum_paths, from the entry's path_counts in one extra launch per sink outside every timed window).
 """
 import argparse
 import json
@@ -94,13 +100,15 @@ def main():
     ap.add_argument("--recipes", default=",".join(RECIPES))
     ap.add_argument("--md", default=None, help="also write the result table (markdown) to this file")
     ap.add_argument("--deterministic", action="store_true", help="add the deterministic arm (fixed-point dSrc) beside the others")
+    ap.add_argument("--presum", action="store_true", help="add the two pre-summed arms (atomic and deterministic); implies --deterministic")
     args = ap.parse_args()
+    args.deterministic = args.deterministic or args.presum
 
     from dmvsnet_amd import cost_agg, ops, synth
     assert torch.cuda.is_available(), "the benchmark needs the MI355X"
     dev = torch.device("cuda:0")
     out = dict(bench="costagg_train", device=torch.cuda.get_device_name(0), reps=args.reps, windows=args.windows,
-               deterministic=args.deterministic, recipes={})
+               deterministic=args.deterministic, presum=args.presum, recipes={})
     for recipe in args.recipes.split(","):
         Hf, Wf, V = RECIPES[recipe]
         cams = synth.synth_cameras(Hf, Wf, V)
@@ -124,9 +132,17 @@ def main():
             def det():
                 torch.autograd.grad(cost_agg(feats, pairs, depth, deterministic=True), feats, gsim)
 
+            def presum():
+                torch.autograd.grad(cost_agg(feats, pairs, depth, deterministic=False, presum=True), feats, gsim)
+
+            def presum_det():
+                torch.autograd.grad(cost_agg(feats, pairs, depth, deterministic=True, presum=True), feats, gsim)
+
             arms = {"fused": fused, "aten": aten}
             if args.deterministic:
                 arms["det"] = det
+            if args.presum:
+                arms.update(presum=presum, presum_det=presum_det)
             for fn in arms.values():
                 fn()
             torch.cuda.synchronize()
@@ -155,6 +171,8 @@ def main():
                     r[k] = float(np.median([window(fn, args.reps) for _ in range(args.windows)]))
                 if args.deterministic:
                     r.update(det_parts(ops, q4, proj12, depth[0], gsim[0], V, C, H, W, args))
+                if args.presum:
+                    r.update(presum_parts(ops, q4, proj12, depth[0], gsim[0], V, C, H, W, args))
             payload = (V - 1) * D * H * W * 4 * C * 4
             r["bwd_src_atomic_bytes"] = payload
             r["bwd_src_atomic_tb_per_s"] = payload / (r["bwd_src_ms"] * 1e-3) / 1e12
@@ -184,6 +202,10 @@ def main():
         if args.deterministic:
             tot.update({k: sum(rw[k] for rw in rows.values()) for k in ("det_scatter_ms", "det_workspace_bytes", "det_atomic_bytes")})
             tot["det_bwd_src_ms"] = sum(rw["det_bwd_src_ms"]["median"] for rw in rows.values())
+        if args.presum:
+            tot.update({k: sum(rw[k]["median"] for rw in rows.values()) for k in ("presum_ms", "presum_det_ms")})
+            tot["presum_src_ms"] = {arm: {q: sum(rw["presum_src_ms"][arm][q] for rw in rows.values()) for q in ("min", "median", "max")}
+                                    for arm in PRESUM_ARMS}
         tot.update({k: sum(rw[k] for rw in rows.values()) for k in ("bwd_src_ms", "bwd_ref_ms", "fwd_ms", "aten_grid_bwd_ms", "bwd_src_atomic_bytes")})
         out["recipes"][recipe] = dict(views=V, passes=rows, per_sample=tot)
     print(json.dumps(out))
@@ -229,6 +251,38 @@ def det_parts(ops, q4, proj12, depth, gsim, V, C, H, W, args):
     return r
 
 
+PRESUM_ARMS = ("atomic", "presum", "det", "presum_det")
+
+
+def presum_parts(ops, q4, proj12, depth, gsim, V, C, H, W, args):
+    """The four source-gradient launches alone (reference gradient off), windows alternating, and the paths the pre-summed
+    scatter's workgroups took (one extra launch per sink, outside the timed windows)."""
+    dev = depth.device
+    gsrc = [torch.zeros((C, H, W), device=dev) for _ in range(V - 1)]
+    ws = torch.empty((ops.warp_corr_backward_det_workspace(C, H, W, V - 1) // 8,), dtype=torch.int64, device=dev)
+    head = (q4[0], q4[1:], proj12, depth, gsim, None, gsrc)
+    runs = {"atomic": lambda: ops.warp_corr_backward(*head),
+            "presum": lambda: ops.warp_corr_backward_presum(*head),
+            "det": lambda: ops.warp_corr_backward_det(*head, workspace=ws),
+            "presum_det": lambda: ops.warp_corr_backward_presum(*head, deterministic=True, workspace=ws)}
+    for fn in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in runs}
+    for w in range(args.windows):
+        for k in (list(runs) if w % 2 == 0 else list(runs)[::-1]):
+            ms[k].append(window(runs[k], args.reps))
+    r = dict(presum_src_ms={k: spread(v) for k, v in ms.items()}, presum_paths={}, presum_cap={})
+    for key, det in (("presum", False), ("presum_det", True)):
+        counts = torch.zeros((3,), dtype=torch.int32, device=dev)
+        ops.warp_corr_backward_presum(*head, deterministic=det, workspace=ws if det else None, path_counts=counts)
+        torch.cuda.synchronize()
+        r["presum_paths"][key] = dict(zip(("windowed", "direct", "empty"), counts.tolist()))
+        r["presum_cap"][key] = ops.warp_corr_backward_presum_cap(C, det)
+    del gsrc, ws
+    return r
+
+
 def markdown(out):
     lines = ["# Cost aggregation, forward + backward: fused (K1 + K1b) against ATen grid_sample", "",
              f"`scripts/costagg_train_bench.py` on {out['device']}, one process, arms alternating; median of {out['windows']} windows of "
@@ -262,6 +316,28 @@ def markdown(out):
                           f"({t['det_bwd_src_ms'] / t['bwd_src_ms']:.2f}x); scatter kernels {t['det_scatter_ms']:.2f} ms for "
                           f"{t['det_atomic_bytes'] / 1e9:.2f} GB of 8-byte integer atomics "
                           f"({t['det_atomic_bytes'] / 1e9 / t['det_scatter_ms']:.2f} TB/s)."]
+        if out.get("presum"):
+            sp = lambda x: f"{x['median']:.3f} ({x['min']:.3f} - {x['max']:.3f})"   # noqa: E731
+            share = lambda c: f"{100.0 * c['windowed'] / max(1, sum(c.values())):.1f} / {100.0 * c['direct'] / max(1, sum(c.values())):.1f} / " \
+                              f"{100.0 * c['empty'] / max(1, sum(c.values())):.1f}"   # noqa: E731
+            lines += ["", "Pre-summed scatter (`cost_agg(..., presum=True)`: the scatter's adds summed in LDS windows first) against the plain "
+                          "scatter of the same mode.  The source-gradient launches alone, four arms alternating in windows of their own, "
+                          "median (min - max); paths: % of workgroups windowed / direct (box above the capacity) / empty:", "",
+                      "| pass | dSrc atomic | dSrc presum | presum / atomic | paths (cap " + str(next(iter(r['passes'].values()))['presum_cap']['presum']) +
+                      ") | dSrc deterministic | dSrc presum det | presum / det | paths (cap " +
+                      str(next(iter(r['passes'].values()))['presum_cap']['presum_det']) + ") | fused fwd+bwd | presum fwd+bwd | det fwd+bwd | presum det fwd+bwd |",
+                      "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+            for name, p in r["passes"].items():
+                m, c = p["presum_src_ms"], p["presum_paths"]
+                lines.append(f"| {name} | {sp(m['atomic'])} | {sp(m['presum'])} | {m['presum']['median'] / m['atomic']['median']:.2f} | {share(c['presum'])} | "
+                             f"{sp(m['det'])} | {sp(m['presum_det'])} | {m['presum_det']['median'] / m['det']['median']:.2f} | {share(c['presum_det'])} | "
+                             f"{sp(p['fused_ms'])} | {sp(p['presum_ms'])} | {sp(p['det_ms'])} | {sp(p['presum_det_ms'])} |")
+            t = r["per_sample"]
+            m = t["presum_src_ms"]
+            lines += ["", "Per sample, dSrc launches summed over the passes, median (sum of minima - sum of maxima): " +
+                      "; ".join(f"{k} {sp(m[k])} ms" for k in PRESUM_ARMS) +
+                      f".  Forward + backward: fused {t['fused_ms']:.2f}, presum {t['presum_ms']:.2f}, deterministic {t['det_ms']:.2f}, "
+                      f"presum deterministic {t['presum_det_ms']:.2f} ms."]
         t = r["per_sample"]
         lines += ["", f"Per sample: fused {t['fused_ms']:.2f} ms, ATen {t['aten_ms']:.2f} ms ({t['aten_ms'] / t['fused_ms']:.2f}x); "
                       f"dSrc kernels {t['bwd_src_ms']:.2f} ms for {t['bwd_src_atomic_bytes'] / 1e9:.2f} GB of atomic payload, "
